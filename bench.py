@@ -28,6 +28,10 @@ metric is the sustained rate of a renderer that is running; and with frames rend
 measured launch choice of this configuration has settled (`config.settle_frames`; a handful when
 profiles/launch_choices.bin -- vr_import_choices -- already holds it).  Then W warm-up steps, a barrier,
 EXACTLY K timed steps, a barrier.  `config.clock_ramp_frames` records it; 0 switches both off.
+
+A plain run stops there: it writes the frame of the last timed step (--dump-outputs DIR) and prints the line.
+Everything that takes runs of its own -- the measured stream-read rate in `roofline`, `cpu_baseline`, `extras`
+(the secondary regimes and the other BASELINE configs) -- is measured only with --full (--extras implies it).
 """
 from __future__ import annotations
 
@@ -88,12 +92,18 @@ def parse_args():
                     help="blob of settled launch choices (vr_import_choices) loaded into every renderer of this run when it was measured by this build on "
                          "this device model; 'none' = start cold")
     ap.add_argument("--save-choices", action="store_true", help="write what this run's renderers settled on back to --choices (merged with what was imported)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the line's own measurement, also measure what takes runs of its own: the stream-read rate in "
+                         "`roofline`, `cpu_baseline` and `extras` (N=1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step as DIR/frame.npy (float32; a fixed, seeded sample of rows, "
+                         "DIR/frame_rows.npy + DIR/frame_row_index.npy, when the frame is above 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without `cpu_baseline`")
     ap.add_argument("--cpu-row-stride", type=int, default=0, help="0 = auto (about 15 s of CPU work)")
     ap.add_argument("--extras", action="store_true",
-                    help="also time the slow secondary measurements (PCIe read-back, orbiting camera); the secondary "
-                         "kernel regimes (unpacked, shallow, off-axis, trilinear) are always in `extras` at N=1")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary kernel regimes")
+                    help="implies --full; also time the slow secondary measurements (PCIe read-back, orbiting camera); the secondary "
+                         "kernel regimes (unpacked, shallow, off-axis, trilinear) are always in `extras` of a --full run at N=1")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the secondary kernel regimes")
     ap.add_argument("--native-group", action="store_true",
                     help="N > 1 without torch.distributed: ONE process drives --gpus members through the C ABI's vr_group_* "
                          "(a renderer per device, RCCL send/recv gather to device 0, assembly kernel there); when the box has "
@@ -102,7 +112,9 @@ def parse_args():
                     help="render a volume file (.raw + .raw.inf, or .pvm) instead of the synthetic volume; --bytes gives its "
                          "voxel size.  VR_DATA_BONSAI / VR_DATA_HEAD name the reference's two datasets (README.md:6-7) for "
                          "--dataset bonsai / --dataset head")
-    return ap.parse_args()
+    args = ap.parse_args()
+    args.full = args.full or args.extras
+    return args
 
 
 def self_launch(args, run=None) -> int:
@@ -198,6 +210,8 @@ def run_native_group(args) -> int:
     ms_per_step = (time.perf_counter() - t0) * 1e3 / args.steps
     kernel_ms = g.kernelMsTake() / args.steps
     frame = g.readPixels()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, frame)
     with vra.RendererCore(devices[0]) as single:          # untimed self-check against one device's own full frame
         single.setup((W, H)); configure(single)
         single.render()
@@ -483,6 +497,8 @@ def main():
         dist.all_gather_object(per_rank, round(kernel_ms, 4), group=host_pg)
         per_rank_kernel_ms = per_rank
     ms_per_step = elapsed * 1e3 / args.steps
+    if args.dump_outputs and rank == 0 and frame is not None:      # (rank 0 holds the whole frame with either collective)
+        dump_outputs(args.dump_outputs, frame.cpu().numpy())
 
     # untimed self-check of the N > 1 path: the gathered frame must equal this rank's own
     # full-frame render bit for bit
@@ -585,16 +601,15 @@ def main():
                 result["binding_bound"] = top["name"] + (" (modelled)" if top["kind"].startswith("MODELLED") else "")
             else:
                 result["binding_bound"] = "hbm (no counter pass committed for these sources)"
-        if world == 1:
+        packed = r.pack12Bytes() if world == 1 else 0
+        if packed:      # the launch gathered from the lossless 12-bit copy (1.5 B per voxel)
+            result["config"]["resident_copy"] = f"12-bit packed copy of the uint16 volume ({packed} B) for the prefix gathers"
+        if world == 1 and args.full:
             # the box's own achievable HBM read rate (streaming read of the resident volume),
             # measured after the timed region ("confirm the peak on the box")
             try:
                 stream_gbps = r.measureStreamRead(5)
-                vol_bytes = int(dims[0]) * int(dims[1]) * int(dims[2]) * b
-                packed = r.pack12Bytes()
-                if packed:      # the launch gathered from the lossless 12-bit copy (1.5 B per voxel)
-                    result["config"]["resident_copy"] = f"12-bit packed copy of the uint16 volume ({packed} B) for the prefix gathers"
-                    vol_bytes = packed
+                vol_bytes = packed or int(dims[0]) * int(dims[1]) * int(dims[2]) * b
                 result["roofline"]["measured_stream_read"] = round(stream_gbps, 1)
                 # reading the volume once + writing the frame at that rate: the floor of any layout
                 result["roofline"]["compulsory_floor_ms"] = round((vol_bytes + W * H * 16) / stream_gbps / 1e6, 4)
@@ -608,12 +623,12 @@ def main():
             result["per_rank_kernel_ms"] = per_rank_kernel_ms
             result["config"]["launcher"] = "torch.distributed.run (one process per GPU)"
             result["overlap"] = f"{args.collective} of frame i on a second stream overlaps the kernel of frame i+1"
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args, r, frame, value)
-        if world == 1 and not args.no_extras and not args.shard:
+        if world == 1 and args.full and not args.no_extras and not args.shard:
             result["extras"] = extras(args, r, local, stream, b, W, H)
     choices_collect(r)
-    if rank == 0 and world == 1 and not args.no_extras and not args.shard and not args.dataset and args.volume == 1024 and not args.dims:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and not args.shard and not args.dataset and args.volume == 1024 and not args.dims:
         # the other BASELINE configs (1, 2, 4), each on its own renderer; the headline's volume is released first
         r.close()
         try:
@@ -631,6 +646,28 @@ def main():
             print(f"[bench] {len(merged)} bytes of settled launch choices written to {args.choices}", file=sys.stderr)
     if result is not None:
         print(json.dumps(result), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6         # all files of --dump-outputs together, .npy headers included
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the frame the last timed step rendered (what vr_read_pixels hands a caller), float32.  The inputs
+    are generated from fixed seeds, so two builds run with the same arguments compare output for output.  A frame above
+    64 MB is sampled: a fixed, seeded set of rows and their indices."""
+    import numpy as np
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes + 4096 <= DUMP_LIMIT_BYTES:
+        np.save(d / "frame.npy", frame)
+        return
+    row_bytes = frame.nbytes // frame.shape[0]
+    n = (DUMP_LIMIT_BYTES - 4096) // (row_bytes + 8)
+    rows = np.sort(np.random.default_rng(0).choice(frame.shape[0], size=n, replace=False))
+    np.save(d / "frame_rows.npy", frame[rows])
+    np.save(d / "frame_row_index.npy", rows.astype(np.float64))
 
 
 CHOICES = {"blob": None, "imported": 0, "exported": []}
@@ -765,7 +802,9 @@ def cpu_baseline(args, r, frame, gpu_msamples):
 
     # the OpenMP row-parallel variant of the same oracle on every host core: a
     # contiguous block of rows about the image centre sized for ~5 s
-    cores = os.cpu_count() or 1
+    # the host cores this process may use (its affinity mask, at most OMP_NUM_THREADS when that is set), not the whole machine's
+    cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    cores = min(cores, int((os.environ.get("OMP_NUM_THREADS") or str(cores)).split(",")[0]))
     all_cores = None
     if cores > 1:
         per_row = max(ps / len(probe_rows), 1.0)

@@ -7,6 +7,7 @@ frames it produces travel as tests/golden/ref_gl/*.npz (see mint_ref_gl_goldens.
 from __future__ import annotations
 
 import ctypes as C
+import os
 import subprocess
 from pathlib import Path
 
@@ -33,7 +34,8 @@ class _Job(C.Structure):
 
 
 def available() -> bool:
-    return SHADER_PATH.exists() and DRIVER_PATH.exists()
+    # (os.access, not Path.exists: a tree this user may not read counts as absent instead of raising PermissionError)
+    return os.access(SHADER_PATH, os.R_OK) and os.access(DRIVER_PATH, os.R_OK)
 
 
 def build() -> Path:

@@ -77,7 +77,7 @@ def test_manifest_is_a_real_gl_run_of_the_reference_shader():
     assert "Mesa" in MANIFEST["gl"] and "llvmpipe" in MANIFEST["gl"]
     assert len(MANIFEST["shader_sha256"]) == 64
     ref = Path("/root/reference/VolumeRenderer.cs")
-    if ref.exists():   # authoring container: the shader that was run is the file as it lies
+    if os.access(ref, os.R_OK):   # authoring container: the shader that was run is the file as it lies
         assert hashlib.sha256(ref.read_bytes()).hexdigest() == MANIFEST["shader_sha256"]
     for name in CASES:
         assert (GOLD / "ref_gl" / f"{name}.npz").exists(), name
