@@ -156,6 +156,38 @@ int vr_set_skip_empty(vr_handle h, int enable);      /* exact empty-space skippi
                                                         counts are bit-identical with it; NEAREST kernels per ray and batch, the
                                                         LDS-staged TRILINEAR kernel per tile and brick layer (round 5), tiles on
                                                         global taps per ray and batch.  No reference equivalent                  */
+/* First-hit isosurface mode (no reference equivalent; the reference's GUI labels CT values in Hounsfield units,
+   src/RendererGUI.cpp:371-411).  enable = 1: every frame shows the surface where the sampled data first reach iso_value,
+   lit by a headlight, and stores its depth (vr_read_depth); the MIP / composite settings are ignored while it is on and
+   kept, so enable = 0 restores the earlier mode unchanged.  Default off.  iso_value is in the units of vr_set_window.
+   Per pixel, each step one correctly rounded fp32 operation in the order given (no rsqrt / pow / fast math; the only fused
+   operations are TRILINEAR's lerps, as in the composite mode):
+   1. Ray and positions: those of the composite mode -- the ray, the box intersection, p0 = start + dir * EPSILON, the
+      composite step, both VR_ACCUM_* modes, the view's texture-coordinate mapping, the box-exit test without its dest.a
+      term, max_steps.  s_i = the filtered raw voxel value at sample i (before the window), either filter.
+   2. Hit: the first step i with s_i >= iso_s; iso_s = float(iso_value + 1000) for 16-bit data under VR_QUIRK_U16_OFFSET,
+      float(iso_value) otherwise.
+   3. Refinement: i = 0: h = q_0.  Else f = (iso_s - s_{i-1}) / (s_i - s_{i-1}) and per component h = q_{i-1} + f * (q_i - q_{i-1})
+      (the difference, then the product, then the sum).
+   4. Normal: central differences of the same sampler at h, g_a = S(+1) - S(-1) along each volume axis a -- TRILINEAR at the
+      continuous voxel coordinates u +- 1 (u = tc * dim - 0.5), NEAREST at voxel indices i +- 1; clamped to the edge.  Box
+      space: G_a = g_b * (dim_b / ext_a) with b the volume axis behind box axis a (front: x, y, z with z negated; top: x, z, y;
+      bottom: x, z, y with the last two negated).  N = v * (1 / sqrt(dot)), v = -G, dot = (v_z*v_z + v_y*v_y) + v_x*v_x;
+      dot = 0: N = -dir.
+   5. Shading, two-sided headlight L = V = H = -dir: d = (N_z*L_z + N_y*L_y) + N_x*L_x, negated when below 0; spec = d^16 by
+      four squarings; rgb = min(base * (0.15 + 0.65 * d) + 0.2 * spec, 1), alpha 1.  base = the transfer function's rgb at the
+      windowed iso_s (the composite mode's index rule) when one is set, else white.
+   6. Miss (the ray leaves the box or runs out of steps): (0, 0, 0, 0), the reference's background.
+   7. Depth: t = ((h_z - o_z) * d_z + (h_y - o_y) * d_y) + (h_x - o_x) * d_x; +inf on a miss.
+   8. vr_count_samples: the march samples up to and including the hit step (refinement and gradient taps not counted) --
+      without a hit the count of a composite frame at alpha_scale 0.
+   vr_set_skip_empty applies: a cell whose dilated maximum is below iso_s is not sampled (frames, depth and counts are the
+   same bits).  Frames into a VR_FB_GREYALPHA32F target are refused (VR_E_INVALID); a vr_group gathers RGBA, not depth. */
+int vr_set_isosurface(vr_handle h, int enable, int32_t iso_value);
+/* the last isosurface frame's depth: one float per pixel of the colour target, indexed like it (fb_w x fb_h, or
+   vr_local_rows() x fb_w for a compact external target); pixels that frame did not render keep earlier values (+inf
+   initially).  VR_E_INVALID before the first isosurface frame. */
+int vr_read_depth(vr_handle h, float *depth, size_t n_floats);
 /* kernel selection: 0 = automatic (specialised kernels when the configuration allows; launches far from filling the
    chip -- fewer than 256 active 32x16 tiles, 1024 when the view is oblique to the volume axes -- use the 4-wavefront
    relay kernel; the fast kernel runs its software-pipelined batch loop unless alpha_scale >= 0.5),

@@ -33,7 +33,8 @@ tools/pmc.sh ${TAG}_tslab_offaxis_sq "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS S
 # ... and what every renderer of the full bench (extras, the other BASELINE configs) settles on joins the blob: the PMC passes of phase B
 # and the bench lines of phase C then all start from settled choices
 python bench.py --extras --save-choices > $OUT/bench_cold_extras.json 2> $OUT/bench_cold_extras.err
-cp profiles/launch_choices.bin $OUT/launch_choices.bin; cp profiles/traffic.json $OUT/traffic.json; cp profiles/valu.json $OUT/valu.json
+python tools/choices_text.py encode    # the committed form of the blob: profiles/launch_choices.json
+cp profiles/launch_choices.bin $OUT/launch_choices.bin; cp profiles/launch_choices.json $OUT/launch_choices.json; cp profiles/traffic.json $OUT/traffic.json; cp profiles/valu.json $OUT/valu.json
 fi
 # 3) HBM traffic + VALU counts of every configuration bench.py reports under `extras` (incl. the MIP / rotated-view entries of round 6)
 if has B; then

@@ -15,6 +15,7 @@
 
 #include "tile_schedule.h"
 #include "volume_io.h"
+#include "vr_iso.h"
 #include "vr_kernels.h"
 
 namespace vr {
@@ -53,6 +54,7 @@ RendererCore::~RendererCore()
         if (d_tile_table_small_) (void)hipFree(d_tile_table_small_);
         if (d_tile_work_) (void)hipFree(d_tile_work_);
         if (d_spp_) (void)hipFree(d_spp_);
+        if (d_depth_) (void)hipFree(d_depth_);
         if (d_scratch_) (void)hipFree(d_scratch_);
         if (d_rgba8_) (void)hipFree(d_rgba8_);
         releasePresent();
@@ -164,6 +166,7 @@ bool RendererCore::loadShader(std::string fn, bool reload)
     if (device_ >= 0) {
         requireDevice("loadShader");
         check(launch_warm_modules(stream()), "module pre-load");
+        check(launch_warm_iso(stream()), "module pre-load (isosurface)");
         check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
         tslab_warm_ = false;
         if (filter == 1) warmTrilinear();
@@ -615,7 +618,8 @@ void RendererCore::buildFrame(FrameParams &P, LaunchConfig &L)
     // (oracle/ref_gl/probe_arith.py); .xzy in rayMarchVolume, .xyz in MIP
     const float num = std::sqrt((e2 * e2 + e1 * e1) + e0 * e0);
     const float fx = (float)nx, fy = (float)ny, fz = (float)nz;
-    const float den = u_.is_MIP == 1 ? std::sqrt((fz * fz + fy * fy) + fx * fx) : std::sqrt((fy * fy + fz * fz) + fx * fx);
+    // (the isosurface mode marches the composite mode's positions, whatever the MIP switch says)
+    const float den = (u_.is_MIP == 1 && !iso_enable_) ? std::sqrt((fz * fz + fy * fy) + fx * fx) : std::sqrt((fy * fy + fz * fz) + fx * fx);
     P.step = num / den;
     P.alpha_scale = u_.alpha_scale;
     P.min_val = u_.min_val; P.max_val = u_.max_val;
@@ -630,7 +634,7 @@ void RendererCore::buildFrame(FrameParams &P, LaunchConfig &L)
 
     L.bytes_per_voxel = res_bytes_;
     L.filter = filter;
-    L.mip = u_.is_MIP;
+    L.mip = iso_enable_ ? 0 : u_.is_MIP;
     L.layout = vol_layout_;
     L.generic = force_generic == 1 ? 1 : 0;
     // kernel variants 6 .. 11: TRILINEAR on the LDS-staged kernel wherever it is eligible, in one of its shapes (0: see refreshTileSchedule)
@@ -680,8 +684,16 @@ void RendererCore::setFramebufferFormat(int fmt)
 
 // everything a launch needs that may touch the host or synchronise (certification, skip grid,
 // tile order, packed copy): done BEFORE the timed region of render()
+// an isosurface frame is RGBA: a (grey, alpha) target is refused -- before the device checks, it is a configuration error
+void RendererCore::refuseIsoGreyAlpha() const
+{
+    if (iso_enable_ && fb_format_ == 1 && ext_fb_)
+        throw std::invalid_argument("render: the (grey, alpha) target format needs a grey mode (the isosurface mode is not one)");
+}
+
 float4 *RendererCore::prepareLaunch(FrameParams &P, LaunchConfig &L)
 {
+    refuseIsoGreyAlpha();
     requireDevice("render");
     if (!cs_program_) throw std::runtime_error("render: no shader loaded (call loadShader first)");
     if (!d_vol_) throw std::runtime_error("render: no dataset loaded");
@@ -689,6 +701,31 @@ float4 *RendererCore::prepareLaunch(FrameParams &P, LaunchConfig &L)
     if (!fb) throw std::runtime_error("render: setup() has not allocated the framebuffer");
     if (fb_format_ == 1 && ext_fb_ && !tf_lut_.empty())
         throw std::invalid_argument("render: the (grey, alpha) target format needs a grey mode (no transfer function)");
+    if (iso_enable_) {
+        // the isosurface kernel (vr_iso.hip): one kernel, no measured choice, no tile table or speed copies; the skip grid when
+        // skipping is on and some cell lies below the iso value
+        refuseIsoGreyAlpha();
+        buildFrame(P, L);
+        P.skip_empty = 0;
+        iso_skip_grid_ = nullptr;
+        if (skip_empty && ensureSkipGrid() && (float)skip_grid_min_ < isoStored()) {
+            P.cnx = (int32_t)((res_dims_[0] + 7) / 8); P.cny = (int32_t)((res_dims_[1] + 7) / 8); P.cnz = (int32_t)((res_dims_[2] + 7) / 8);
+            iso_skip_grid_ = d_skip_grid_;
+        }
+        const int rows = std::max(localRows(), framebuffer_size[1]);
+        const size_t n = (size_t)rows * (size_t)framebuffer_size[0];
+        if (depth_capacity_ < n) {
+            if (d_depth_) { check(hipFree(d_depth_), "hipFree(depth)"); d_depth_ = nullptr; depth_capacity_ = 0; }
+            check(hipMalloc(reinterpret_cast<void **>(&d_depth_), std::max<size_t>(n, 1) * sizeof(float)), "hipMalloc(depth)");
+            depth_capacity_ = n;
+            check(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_depth_), 0x7f800000, n, stream()), "hipMemset(depth)");   // +inf
+        }
+        depth_rows_ = (ext_fb_ && fb_compact_) ? localRows() : framebuffer_size[1];
+        depth_w_ = framebuffer_size[0];
+        tune_measure_ = false;
+        last_choice_ = 0;
+        return fb;
+    }
     if (filter == 1) warmTrilinear();          // (a caller that set the public field directly; a no-op once done)
     buildFrame(P, L);
     refreshSkipGrid(P, L);
@@ -724,7 +761,7 @@ void RendererCore::launch(uint32_t *spp)
     const bool measure = tune_measure_ && spp == nullptr && tune_count_ < kTuneSlots;
     TuneSlot &slot = tune_slot_[(tune_head_ + tune_count_) % kTuneSlots];
     if (measure) check(hipEventRecord(slot.ev0, stream()), "hipEventRecord");
-    check(launch_raymarch(P, L, d_vol_, d_tf_, fb, spp, stream(), &last_kernel_), "raymarch launch");
+    check(launchKernel(P, L, fb, spp), "raymarch launch");
     if (measure) {
         check(hipEventRecord(slot.ev1, stream()), "hipEventRecord");
         slot.key = tune_key_; slot.cand = tune_cand_; slot.gen = tune_gen_;
@@ -1220,6 +1257,24 @@ void RendererCore::refreshSkipGrid(FrameParams &P, LaunchConfig &L)
     const uint32_t cnx = (uint32_t)(nx + 7) / 8, cny = (uint32_t)(ny + 7) / 8, cnz = (uint32_t)(nz + 7) / 8;
     const size_t cells = (size_t)cnx * cny * cnz;
     if (cells * 2 >= (1ull << 32) || cnx >= (1u << 24) || (uint64_t)cny * cnz >= (1u << 24)) return;
+    if (!ensureSkipGrid()) return;
+    // nothing to skip at this threshold (a window that starts at the data's floor): the launch takes the instances without
+    // skipping -- theirs are the leaner loops (staged TRILINEAR 3.8 %, its tiles on global taps 20 %, the NEAREST kernels a
+    // workgroup of occupancy).  A host comparison against the grid's smallest cell: no device work, no synchronisation per frame.
+    if (thresh < (int)skip_grid_min_) return;
+    P.skip_empty = 1;
+    P.skip_thresh = thresh;
+    P.cnx = (int32_t)cnx; P.cny = (int32_t)cny; P.cnz = (int32_t)cnz;
+    L.skip_grid = d_skip_grid_;
+    L.skip_grid_bytes = (uint32_t)(cells * sizeof(uint16_t));
+}
+
+bool RendererCore::ensureSkipGrid()
+{
+    const int nx = res_dims_[0], ny = res_dims_[1], nz = res_dims_[2];
+    const uint32_t cnx = (uint32_t)(nx + 7) / 8, cny = (uint32_t)(ny + 7) / 8, cnz = (uint32_t)(nz + 7) / 8;
+    const size_t cells = (size_t)cnx * cny * cnz;
+    if (cells * 2 >= (1ull << 32) || cnx >= (1u << 24) || (uint64_t)cny * cnz >= (1u << 24)) return false;
     if (!d_skip_grid_) {
         uint16_t *tmp = nullptr;
         check(hipMalloc(reinterpret_cast<void **>(&tmp), std::max<size_t>(cells * sizeof(uint16_t), 8)), "hipMalloc(skip grid tmp)");   // (also holds the one-word minimum below)
@@ -1238,15 +1293,7 @@ void RendererCore::refreshSkipGrid(FrameParams &P, LaunchConfig &L)
         skip_grid_cells_ = cells;
         skip_grid_min_ = gmin;
     }
-    // nothing to skip at this threshold (a window that starts at the data's floor): the launch takes the instances without
-    // skipping -- theirs are the leaner loops (staged TRILINEAR 3.8 %, its tiles on global taps 20 %, the NEAREST kernels a
-    // workgroup of occupancy).  A host comparison against the grid's smallest cell: no device work, no synchronisation per frame.
-    if (thresh < (int)skip_grid_min_) return;
-    P.skip_empty = 1;
-    P.skip_thresh = thresh;
-    P.cnx = (int32_t)cnx; P.cny = (int32_t)cny; P.cnz = (int32_t)cnz;
-    L.skip_grid = d_skip_grid_;
-    L.skip_grid_bytes = (uint32_t)(cells * sizeof(uint16_t));
+    return true;
 }
 
 // Rebuild the longest-first block order when the camera / image / shard changed.  The
@@ -1383,6 +1430,7 @@ void RendererCore::refreshTileSchedule(const FrameParams &P, LaunchConfig &L)
 
 void RendererCore::render()
 {
+    refuseIsoGreyAlpha();
     requireDevice("render");
     // the reference brackets glDispatchCompute with a GL_TIME_ELAPSED query and blocks
     // on its result (src/RendererCore.cpp:149-153); same shape with HIP events
@@ -1395,13 +1443,40 @@ void RendererCore::render()
     const int mcand = tune_cand_;
     tune_measure_ = false;
     check(hipEventRecord(ev0_, stream()), "hipEventRecord");
-    check(launch_raymarch(P, L, d_vol_, d_tf_, fb, nullptr, stream(), &last_kernel_), "raymarch launch");
+    check(launchKernel(P, L, fb, nullptr), "raymarch launch");
     check(hipEventRecord(ev1_, stream()), "hipEventRecord");
     check(hipEventSynchronize(ev1_), "hipEventSynchronize");
     float ms = 0.0f;
     check(hipEventElapsedTime(&ms, ev0_, ev1_), "hipEventElapsedTime");
     kerneltime_sum += ms;
     if (measure) { tuneIssued(mkey, mgen, mcand); tuneRecord(mkey, mgen, mcand, ms); }   // the blocking path measures anyway
+}
+
+hipError_t RendererCore::launchKernel(const FrameParams &P, const LaunchConfig &L, float4 *fb, uint32_t *spp)
+{
+    if (!iso_enable_) return launch_raymarch(P, L, d_vol_, d_tf_, fb, spp, stream(), &last_kernel_);
+    IsoArgs A;
+    A.iso_s = isoStored();
+    A.depth = d_depth_;
+    A.skip_grid = iso_skip_grid_;
+    return launch_raymarch_iso(P, L, A, d_vol_, d_tf_, fb, spp, stream(), &last_kernel_);
+}
+
+// iso_s = float(iso + 1000) for 16-bit data under VR_QUIRK_U16_OFFSET (the window's own offset, setMinVal), float(iso) otherwise
+float RendererCore::isoStored() const
+{
+    const bool offset = datasize_bytes == 2 && (quirks & kQuirkU16Offset);
+    return (float)((int64_t)iso_value_ + (offset ? 1000 : 0));
+}
+
+void RendererCore::readDepth(float *depth, size_t n_floats)
+{
+    requireDevice("readDepth");
+    if (depth_rows_ < 0 || !d_depth_) throw std::invalid_argument("readDepth: no isosurface frame has been rendered");
+    const size_t n = (size_t)depth_rows_ * (size_t)depth_w_;
+    if (!depth || n_floats < n) throw std::invalid_argument("readDepth: buffer too small");
+    check(hipMemcpyAsync(depth, d_depth_, n * sizeof(float), hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H depth)");
+    check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
 }
 
 void RendererCore::renderAsync()
@@ -1417,6 +1492,7 @@ void RendererCore::synchronize()
 
 void RendererCore::countSamples(uint64_t *total, uint32_t *per_pixel, size_t n_pixels)
 {
+    refuseIsoGreyAlpha();
     requireDevice("countSamples");
     const size_t n = (size_t)framebuffer_size[0] * (size_t)framebuffer_size[1];
     if (per_pixel && n_pixels < n) throw std::invalid_argument("countSamples: per_pixel buffer too small");

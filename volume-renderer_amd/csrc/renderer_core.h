@@ -85,7 +85,7 @@ public:
     void *framebufferDevice() const { return ext_fb_ ? ext_fb_ : d_fb_; }
     void setStream(hipStream_t s) { user_stream_ = s; }
     hipStream_t streamHandle() const { return stream(); }     // the stream the next launch goes to
-    bool greyMode() const { return tf_lut_.empty(); }          // r == g == b in every pixel (no transfer function)
+    bool greyMode() const { return tf_lut_.empty() && !iso_enable_; }   // r == g == b in every pixel (no transfer function, no isosurface)
     void prepareForLaunch() { FrameParams P; LaunchConfig L; (void)prepareLaunch(P, L); }   // certification, tile order, packed copy: host work a timed launch should not carry
     void setExternalFramebuffer(void *p) { ext_fb_ = p; }
     void setRowRange(int b, int e) { row_begin_ = b; row_end_ = e; }
@@ -116,6 +116,11 @@ public:
     uint64_t copyBudget() const { return copy_budget_; }
     bool hasDevice() const { return device_ >= 0; }
     void warmTrilinear();                    // pre-load the staged TRILINEAR kernel's code objects (once)
+    // first-hit isosurface mode (vr_set_isosurface): while on, frames are the shaded surface and its depth, whatever the MIP /
+    // composite settings, which are kept for when it is switched off.  iso in the window's units (vr_set_window).
+    void setIsosurface(bool enable, int32_t iso) { iso_enable_ = enable; iso_value_ = iso; }
+    bool isosurfaceEnabled() const { return iso_enable_; }
+    void readDepth(float *depth, size_t n_floats);   // the last iso frame's depth target (rows x fb_w floats, indexed like the colour target)
 
     int filter = 0, accum = 0, skip_empty = 0;
     int layout = 1;          // VR_LAYOUT_BRICKED: the faster HBM layout is the default (vr_set_layout)
@@ -158,6 +163,12 @@ private:
     bool tf_grey_ = false;                   // every entry of tf_lut_ has r == g == b bit for bit
     int exact_min_ = 0, exact_max_ = 65535;   // exact voxel range of the resident volume
     int row_begin_ = 0, row_end_ = -1;
+    bool iso_enable_ = false;
+    int32_t iso_value_ = 0;
+    float *d_depth_ = nullptr;               // depth target of the iso frames (+inf where no surface; allocated on the first one)
+    size_t depth_capacity_ = 0;              // floats
+    int depth_rows_ = -1, depth_w_ = 0;      // rows x width the last iso frame's depth is indexed by (-1: no iso frame yet)
+    float isoStored() const;                 // the iso value in stored voxel units (the +1000 of VR_QUIRK_U16_OFFSET included)
     int stripe_rows_ = 0, stripe_index_ = 0, stripe_count_ = 1;
     bool fb_compact_ = false;
     int fb_format_ = 0;
@@ -191,6 +202,10 @@ private:
     size_t skip_grid_cells_ = 0;
     unsigned skip_grid_min_ = 0;             // smallest cell value of the grid (read back once when it is built): a threshold below it skips nothing and the launch keeps the instances without skipping
     void refreshSkipGrid(FrameParams &P, LaunchConfig &L);
+    void refuseIsoGreyAlpha() const;
+    bool ensureSkipGrid();                   // build the dilated cell-max grid if it is not resident; false = the volume is too large for it
+    const uint16_t *iso_skip_grid_ = nullptr;   // the grid the iso launch being prepared skips on (nullptr = no skipping)
+    hipError_t launchKernel(const FrameParams &P, const LaunchConfig &L, float4 *fb, uint32_t *spp);   // the ray-march or the iso kernel
     uint32_t *d_tile_table_ = nullptr;       // work-ordered block -> tile table (tile_schedule.h)
     size_t tile_table_capacity_ = 0, tile_table_blocks_ = 0;
     uint32_t *d_tile_table_tall_ = nullptr;  // the same for 16x32-pixel tiles (the staged trilinear kernel's tall shape); built with the table above

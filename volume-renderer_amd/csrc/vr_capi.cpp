@@ -321,6 +321,16 @@ int vr_set_skip_empty(vr_handle h, int enable)
     return guarded(h, [&](vr::RendererCore &c) { c.skip_empty = enable != 0; });
 }
 
+int vr_set_isosurface(vr_handle h, int enable, int32_t iso_value)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.setIsosurface(enable != 0, iso_value); });
+}
+
+int vr_read_depth(vr_handle h, float *depth, size_t n_floats)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.readDepth(depth, n_floats); });
+}
+
 int vr_set_autotune(vr_handle h, int enable)
 {
     if (!h) return VR_E_INVALID;

@@ -117,6 +117,8 @@ def load_library() -> C.CDLL:
         "vr_set_layout": (i32, [h, i32]),
         "vr_set_skip_empty": (i32, [h, i32]),
         "vr_set_kernel_variant": (i32, [h, i32]),
+        "vr_set_isosurface": (i32, [h, i32, C.c_int32]),
+        "vr_read_depth": (i32, [h, C.POINTER(f32), C.c_size_t]),
         "vr_set_autotune": (i32, [h, i32]),
         "vr_export_choices": (i32, [h, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
         "vr_import_choices": (i32, [h, C.c_void_p, C.c_size_t, C.POINTER(i32)]),
@@ -501,6 +503,17 @@ class RendererCore:
         """candidate bits of the last launch: 1 relay, 2 pipelined loop, 4 short batches, staged-trilinear shape << 3,
         256 = a trial frame (the measured choice is still exploring this configuration)"""
         return int(self._lib.vr_get_launch_choice(self._h))
+
+    def setIsosurface(self, enable, iso=0):
+        """first-hit isosurface mode at `iso` (the units of setWindow); the MIP / composite settings are kept for when it is off"""
+        self._check(self._lib.vr_set_isosurface(self._h, int(bool(enable)), int(iso)))
+
+    def readDepth(self, rows=None) -> np.ndarray:
+        """the last isosurface frame's depth [rows, W] float32 (+inf = no surface); rows = localRows() for a compact target"""
+        w, h = self.framebuffer_size
+        out = np.zeros((h if rows is None else int(rows), w), dtype=np.float32)
+        self._check(self._lib.vr_read_depth(self._h, _fp(out), out.size))
+        return out
 
     def setKernelVariant(self, variant):
         self._check(self._lib.vr_set_kernel_variant(self._h, variant))
