@@ -188,6 +188,39 @@ int vr_set_isosurface(vr_handle h, int enable, int32_t iso_value);
    vr_local_rows() x fb_w for a compact external target); pixels that frame did not render keep earlier values (+inf
    initially).  VR_E_INVALID before the first isosurface frame. */
 int vr_read_depth(vr_handle h, float *depth, size_t n_floats);
+/* Multi-planar reslice mode (no reference equivalent): axial, coronal, sagittal or oblique reformats, plain (n = 1) or as a
+   thick slab reduced to its maximum (MIP), minimum (MinIP) or mean, and the value behind each pixel (vr_read_reslice_values).
+   enable = 1: every frame shows the plane; alpha_scale, the MIP switch, the camera, the view and the spacing are ignored while
+   it is on and kept, so enable = 0 restores the earlier mode unchanged.  Default off.  Per pixel, each step one correctly
+   rounded fp32 operation in the order given (nothing contracted; the only fused operations are TRILINEAR's lerps, exactly as
+   in the isosurface mode):
+   1. Geometry: geom12 = o[3], du[3], dv[3], dw[3] in voxel index coordinates (x the fastest volume axis; voxel (i, j, k)'s
+      centre at (i, j, k)); o is the centre of pixel (0, 0).  Pixel (x, y) is numbered by the global column and row of the
+      colour target (as a full-frame vr_read_pixels); X = (float)x, Y = (float)y, p_a = (o_a + X*du_a) + Y*dv_a.
+   2. Slab: n samples, 1 <= n <= 1024; for k = 0 .. n-1, c_k = (float)(2k - (n-1)) * 0.5f (exact), q_a = p_a + c_k*dw_a.
+   3. Inside test: r_a = q_a + 0.5f; the sample is inside when 0 <= r_a < (float)dim_a on all three axes.  Only inside
+      samples are fetched.
+   4. Sampling: NEAREST reads voxel ((int)r_x, (int)r_y, (int)r_z).  TRILINEAR: GL's linear rule at the continuous voxel
+      coordinates (u, v, w) = q, taps clamped to the edge, lerps x then y then z (the isosurface mode's sampler).  s_k is the
+      raw stored value, before the window.
+   5. Reduction over the inside samples in increasing k: VR_SLAB_MIP keeps the max (replacing on s > m), VR_SLAB_MINIP the min
+      (replacing on s < m), VR_SLAB_MEAN acc = acc + s from 0.0f, then value = acc / (float)cnt.  n = 1: the three agree.
+   6. Output: cnt = 0: (0, 0, 0, 0), the background of every mode.  Else v = the composite mode's window of value (max == min:
+      0); without a transfer function (v, v, v, 1), with one (rgb of the LUT at the composite mode's index rule, 1).
+   7. vr_read_reslice_values: value - 1000.0f for 16-bit data under VR_QUIRK_U16_OFFSET (the window's units, HU), value
+      otherwise; the quiet NaN 0x7fc00000 where cnt = 0.
+   8. vr_count_samples: cnt.
+   Row ranges, stripes, compact external targets, VR_QUIRK_TRUNC_GRID and volumes beyond 32-bit offsets apply.  Without a
+   transfer function it is a grey mode (VR_FB_GREYALPHA32F targets, a vr_group's (grey, alpha) gather).  vr_set_skip_empty
+   has no effect; vr_get_launch_choice is 0 after a reslice frame and the measured launch choices are untouched.
+   VR_E_INVALID for an unknown mode, n outside 1..1024, a non-finite geometry float or while the isosurface mode is on (and
+   vr_set_isosurface(h, 1, ...) is refused while this mode is on); enable = 0 ignores the other arguments (may be NULL) and
+   always succeeds. */
+enum { VR_SLAB_MIP = 0, VR_SLAB_MINIP = 1, VR_SLAB_MEAN = 2 };
+int vr_set_reslice(vr_handle h, int enable, const float geom12[12], int slab_mode, int slab_samples);
+/* the last reslice frame's values: one float per pixel of the colour target, indexed like it (as vr_read_depth); pixels that
+   frame did not render keep earlier values (NaN initially).  VR_E_INVALID before the first reslice frame. */
+int vr_read_reslice_values(vr_handle h, float *values, size_t n_floats);
 /* kernel selection: 0 = automatic (specialised kernels when the configuration allows; launches far from filling the
    chip -- fewer than 256 active 32x16 tiles, 1024 when the view is oblique to the volume axes -- use the 4-wavefront
    relay kernel; the fast kernel runs its software-pipelined batch loop unless alpha_scale >= 0.5),

@@ -13,11 +13,13 @@ from .renderer import (  # noqa: F401
     RendererCore,
     RendererGroup,
     VRError,
+    axis_reslice,
     build_library,
     checksum,
     write_image_rgb8,
     load_library,
     read_pvm_volume,
+    reslice_geometry,
     symbols_declared_in_header,
 )
 
@@ -26,10 +28,12 @@ __all__ = [
     "RendererCore",
     "RendererGroup",
     "VRError",
+    "axis_reslice",
     "build_library",
     "checksum",
     "write_image_rgb8",
     "load_library",
     "read_pvm_volume",
+    "reslice_geometry",
     "symbols_declared_in_header",
 ]

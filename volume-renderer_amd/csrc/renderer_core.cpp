@@ -16,6 +16,7 @@
 #include "tile_schedule.h"
 #include "volume_io.h"
 #include "vr_iso.h"
+#include "vr_reslice.h"
 #include "vr_kernels.h"
 
 namespace vr {
@@ -55,6 +56,7 @@ RendererCore::~RendererCore()
         if (d_tile_work_) (void)hipFree(d_tile_work_);
         if (d_spp_) (void)hipFree(d_spp_);
         if (d_depth_) (void)hipFree(d_depth_);
+        if (d_values_) (void)hipFree(d_values_);
         if (d_scratch_) (void)hipFree(d_scratch_);
         if (d_rgba8_) (void)hipFree(d_rgba8_);
         releasePresent();
@@ -167,6 +169,7 @@ bool RendererCore::loadShader(std::string fn, bool reload)
         requireDevice("loadShader");
         check(launch_warm_modules(stream()), "module pre-load");
         check(launch_warm_iso(stream()), "module pre-load (isosurface)");
+        check(launch_warm_reslice(stream()), "module pre-load (reslice)");
         check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
         tslab_warm_ = false;
         if (filter == 1) warmTrilinear();
@@ -722,6 +725,25 @@ float4 *RendererCore::prepareLaunch(FrameParams &P, LaunchConfig &L)
         }
         depth_rows_ = (ext_fb_ && fb_compact_) ? localRows() : framebuffer_size[1];
         depth_w_ = framebuffer_size[0];
+        tune_measure_ = false;
+        last_choice_ = 0;
+        return fb;
+    }
+    if (reslice_enable_) {
+        // the reslice kernel (vr_reslice.hip): one kernel, no measured choice (nothing explored, settled or evicted), no tile
+        // table, speed copies or skip grid
+        buildFrame(P, L);
+        P.skip_empty = 0;
+        const int rows = std::max(localRows(), framebuffer_size[1]);
+        const size_t n = (size_t)rows * (size_t)framebuffer_size[0];
+        if (values_capacity_ < n) {
+            if (d_values_) { check(hipFree(d_values_), "hipFree(values)"); d_values_ = nullptr; values_capacity_ = 0; }
+            check(hipMalloc(reinterpret_cast<void **>(&d_values_), std::max<size_t>(n, 1) * sizeof(float)), "hipMalloc(values)");
+            values_capacity_ = n;
+            check(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_values_), 0x7fc00000, n, stream()), "hipMemset(values)");   // quiet NaN
+        }
+        values_rows_ = (ext_fb_ && fb_compact_) ? localRows() : framebuffer_size[1];
+        values_w_ = framebuffer_size[0];
         tune_measure_ = false;
         last_choice_ = 0;
         return fb;
@@ -1454,6 +1476,15 @@ void RendererCore::render()
 
 hipError_t RendererCore::launchKernel(const FrameParams &P, const LaunchConfig &L, float4 *fb, uint32_t *spp)
 {
+    if (reslice_enable_) {
+        ResliceArgs A;
+        std::memcpy(&A.g, reslice_geom_, sizeof(A.g));
+        A.mode = reslice_mode_;
+        A.n = reslice_n_;
+        A.hu_offset = (datasize_bytes == 2 && (quirks & kQuirkU16Offset)) ? 1 : 0;
+        A.values = d_values_;
+        return launch_reslice(P, L, A, d_vol_, d_tf_, fb, spp, stream(), &last_kernel_);
+    }
     if (!iso_enable_) return launch_raymarch(P, L, d_vol_, d_tf_, fb, spp, stream(), &last_kernel_);
     IsoArgs A;
     A.iso_s = isoStored();
@@ -1476,6 +1507,39 @@ void RendererCore::readDepth(float *depth, size_t n_floats)
     const size_t n = (size_t)depth_rows_ * (size_t)depth_w_;
     if (!depth || n_floats < n) throw std::invalid_argument("readDepth: buffer too small");
     check(hipMemcpyAsync(depth, d_depth_, n * sizeof(float), hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H depth)");
+    check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
+}
+
+void RendererCore::setIsosurface(bool enable, int32_t iso)
+{
+    if (enable && reslice_enable_) throw std::invalid_argument("setIsosurface: the reslice mode is on (switch it off first)");
+    iso_enable_ = enable;
+    iso_value_ = iso;
+}
+
+void RendererCore::setReslice(bool enable, const float *geom12, int mode, int n)
+{
+    if (!enable) { reslice_enable_ = false; return; }
+    if (iso_enable_) throw std::invalid_argument("setReslice: the isosurface mode is on (switch it off first)");
+    if (mode < 0 || mode > 2) throw std::invalid_argument("setReslice: unknown slab mode");
+    if (n < 1 || n > 1024) throw std::invalid_argument("setReslice: slab samples outside 1..1024");
+    if (!geom12) throw std::invalid_argument("setReslice: no geometry");
+    for (int i = 0; i < 12; i++)
+        if (!std::isfinite(geom12[i])) throw std::invalid_argument("setReslice: non-finite geometry");
+    std::memcpy(reslice_geom_, geom12, sizeof(reslice_geom_));
+    reslice_mode_ = mode;
+    reslice_n_ = n;
+    reslice_enable_ = true;
+}
+
+void RendererCore::readResliceValues(float *values, size_t n_floats)
+{
+    // (before the device check: a handle that never rendered a reslice frame has no values, with or without a device)
+    if (values_rows_ < 0 || !d_values_) throw std::invalid_argument("readResliceValues: no reslice frame has been rendered");
+    requireDevice("readResliceValues");
+    const size_t n = (size_t)values_rows_ * (size_t)values_w_;
+    if (!values || n_floats < n) throw std::invalid_argument("readResliceValues: buffer too small");
+    check(hipMemcpyAsync(values, d_values_, n * sizeof(float), hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H values)");
     check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
 }
 

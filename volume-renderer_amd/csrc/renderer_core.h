@@ -85,7 +85,7 @@ public:
     void *framebufferDevice() const { return ext_fb_ ? ext_fb_ : d_fb_; }
     void setStream(hipStream_t s) { user_stream_ = s; }
     hipStream_t streamHandle() const { return stream(); }     // the stream the next launch goes to
-    bool greyMode() const { return tf_lut_.empty() && !iso_enable_; }   // r == g == b in every pixel (no transfer function, no isosurface)
+    bool greyMode() const { return tf_lut_.empty() && !iso_enable_; }   // r == g == b in every pixel (no transfer function, no isosurface; reslice frames without one are grey)
     void prepareForLaunch() { FrameParams P; LaunchConfig L; (void)prepareLaunch(P, L); }   // certification, tile order, packed copy: host work a timed launch should not carry
     void setExternalFramebuffer(void *p) { ext_fb_ = p; }
     void setRowRange(int b, int e) { row_begin_ = b; row_end_ = e; }
@@ -118,9 +118,15 @@ public:
     void warmTrilinear();                    // pre-load the staged TRILINEAR kernel's code objects (once)
     // first-hit isosurface mode (vr_set_isosurface): while on, frames are the shaded surface and its depth, whatever the MIP /
     // composite settings, which are kept for when it is switched off.  iso in the window's units (vr_set_window).
-    void setIsosurface(bool enable, int32_t iso) { iso_enable_ = enable; iso_value_ = iso; }
+    void setIsosurface(bool enable, int32_t iso);   // enable while reslicing: std::invalid_argument
     bool isosurfaceEnabled() const { return iso_enable_; }
     void readDepth(float *depth, size_t n_floats);   // the last iso frame's depth target (rows x fb_w floats, indexed like the colour target)
+    // multi-planar reslice mode (vr_set_reslice): while on, frames are the plane's (slab-reduced) values, windowed; the MIP /
+    // composite settings and the camera are kept for when it is switched off.  geom: o, du, dv, dw in voxel index coordinates.
+    // enable = false ignores the other arguments; a bad mode / n / geometry, or the isosurface mode being on: std::invalid_argument
+    void setReslice(bool enable, const float *geom12, int mode, int n);
+    bool resliceEnabled() const { return reslice_enable_; }
+    void readResliceValues(float *values, size_t n_floats);   // the last reslice frame's values target (as readDepth)
 
     int filter = 0, accum = 0, skip_empty = 0;
     int layout = 1;          // VR_LAYOUT_BRICKED: the faster HBM layout is the default (vr_set_layout)
@@ -169,6 +175,12 @@ private:
     size_t depth_capacity_ = 0;              // floats
     int depth_rows_ = -1, depth_w_ = 0;      // rows x width the last iso frame's depth is indexed by (-1: no iso frame yet)
     float isoStored() const;                 // the iso value in stored voxel units (the +1000 of VR_QUIRK_U16_OFFSET included)
+    bool reslice_enable_ = false;
+    float reslice_geom_[12] = {};            // o, du, dv, dw (vr_reslice.h: ResliceGeom)
+    int reslice_mode_ = 0, reslice_n_ = 1;   // VR_SLAB_*, slab samples
+    float *d_values_ = nullptr;              // values target of the reslice frames (NaN where no sample; allocated on the first one)
+    size_t values_capacity_ = 0;             // floats
+    int values_rows_ = -1, values_w_ = 0;    // rows x width the last reslice frame's values are indexed by (-1: no reslice frame yet)
     int stripe_rows_ = 0, stripe_index_ = 0, stripe_count_ = 1;
     bool fb_compact_ = false;
     int fb_format_ = 0;
@@ -205,7 +217,7 @@ private:
     void refuseIsoGreyAlpha() const;
     bool ensureSkipGrid();                   // build the dilated cell-max grid if it is not resident; false = the volume is too large for it
     const uint16_t *iso_skip_grid_ = nullptr;   // the grid the iso launch being prepared skips on (nullptr = no skipping)
-    hipError_t launchKernel(const FrameParams &P, const LaunchConfig &L, float4 *fb, uint32_t *spp);   // the ray-march or the iso kernel
+    hipError_t launchKernel(const FrameParams &P, const LaunchConfig &L, float4 *fb, uint32_t *spp);   // the ray-march, the iso or the reslice kernel
     uint32_t *d_tile_table_ = nullptr;       // work-ordered block -> tile table (tile_schedule.h)
     size_t tile_table_capacity_ = 0, tile_table_blocks_ = 0;
     uint32_t *d_tile_table_tall_ = nullptr;  // the same for 16x32-pixel tiles (the staged trilinear kernel's tall shape); built with the table above

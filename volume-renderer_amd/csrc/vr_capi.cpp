@@ -331,6 +331,16 @@ int vr_read_depth(vr_handle h, float *depth, size_t n_floats)
     return guarded(h, [&](vr::RendererCore &c) { c.readDepth(depth, n_floats); });
 }
 
+int vr_set_reslice(vr_handle h, int enable, const float geom12[12], int slab_mode, int slab_samples)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.setReslice(enable != 0, geom12, slab_mode, slab_samples); });
+}
+
+int vr_read_reslice_values(vr_handle h, float *values, size_t n_floats)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.readResliceValues(values, n_floats); });
+}
+
 int vr_set_autotune(vr_handle h, int enable)
 {
     if (!h) return VR_E_INVALID;

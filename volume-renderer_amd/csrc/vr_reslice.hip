@@ -1,0 +1,265 @@
+// vr_reslice.hip -- the multi-planar reslice kernel (vr_set_reslice): per pixel a short line of n samples across a plane
+// given in voxel index coordinates, reduced to its maximum, minimum or mean (thick-slab MIP / MinIP / average; n = 1 is a
+// plain slice), windowed like the composite mode, and the raw value stored for read-back.  The definition, step by step, is
+// in include/vr_core.h and DESIGN.md section 1; tests/reslice_ref/reslice_ref.c restates it on the CPU and
+// tests/test_reslice_gpu.py holds this kernel to it bit for bit.
+//
+// Its own translation units (VR_RESLICE_TU = 0: 8-bit volumes and the entry points, 1: 16-bit volumes), like vr_iso.hip: the
+// vr_kernels.hip units, FrameParams and LaunchConfig are untouched by the mode; the plane, the slab and the values target
+// are extra kernel arguments.  Arithmetic contract as in vr_kernels.hip: one correctly rounded fp32 operation per step,
+// nothing contracted (-ffp-contract=off); the only fused operations are explicit: TRILINEAR's lerps (tri_lerp) and the
+// certified window division (div_cert).
+//
+// Shape: the isosurface kernel's -- one pixel per lane, 8x8 pixels per wavefront, 16x16-pixel tiles of four wavefronts dealt
+// to the XCDs by tile_of_block().  A wavefront's 64 lanes sample a compact 8x8 patch of the plane, about 2x2 bricks of 4^3
+// per slab step, so neighbouring lanes share cache lines.  The slab loop is unrolled by 4: four positions, their loads, then
+// the reduction in k order -- several misses in flight per lane without changing the order of the sum.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "vr_device.h"
+#include "vr_reslice.h"
+
+#ifndef VR_RESLICE_TU
+#define VR_RESLICE_TU -1
+#endif
+
+namespace vr {
+
+template <typename VoxelT, int LAYOUT, int FILTER, int MODE, bool BIG>
+__global__ __launch_bounds__(256) void reslice_kernel(const FrameParams P, const ResliceGeom G, const int n, const int divmode,
+                                                      const int hu_offset, const uint32_t vol_bytes, const VoxelT *__restrict__ vol,
+                                                      const float4 *__restrict__ tf, float4 *__restrict__ fb, uint32_t *__restrict__ spp,
+                                                      float *__restrict__ values, const unsigned tiles_x, const unsigned tiles_y)
+{
+    unsigned tx, ty;
+    tile_of_block(blockIdx.x, tiles_x, tiles_y, tx, ty);
+    if (tx == 0xffffffffu) return;
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const int lx = (int)(tx * 16u + (wave & 1u) * 8u + (lane & 7u));
+    const int ly = (int)(ty * 16u + (wave >> 1) * 8u + (lane >> 3));
+    int px = lx, py;
+    if (P.stripe_count > 1) {
+        const int s = ly / P.stripe_rows, r = ly % P.stripe_rows;
+        py = (s * P.stripe_count + P.stripe_index) * P.stripe_rows + r;
+    } else {
+        py = P.row_begin + ly;
+    }
+    if (px >= P.col_lim || py >= P.row_lim || py >= P.row_end) return;
+
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)vol, 0, BIG ? 0 : (int)pair_load_extent(vol_bytes), 0x00020000);
+    // per-axis terms of VoxelAddr<LAYOUT, false>::at(i, j, k) = X(i) + Y(j) + Z(k)  (mod 2^32), as in the generic kernel
+    auto term_x = [&](int i) -> uint32_t {
+        return LAYOUT == 0 ? (uint32_t)i : mad_u24((uint32_t)i >> BRICK_LX, 64u - (uint32_t)BRICK_X, (uint32_t)i);
+    };
+    auto term_y = [&](int j) -> uint32_t {
+        if (LAYOUT == 0) return mad_u24((uint32_t)j, (uint32_t)P.nx, 0u);
+        return mad_u24(BRICK_LY ? (uint32_t)j >> BRICK_LY : (uint32_t)j, P.bstride_y, BRICK_LY ? (uint32_t)j << BRICK_LX : 0u);
+    };
+    auto term_z = [&](int k) -> uint32_t {
+        if (LAYOUT == 0) return mad_u24(mad_u24((uint32_t)k, (uint32_t)P.ny, 0u), (uint32_t)P.nx, 0u);
+        return mad_u24(BRICK_LZ ? (uint32_t)k >> BRICK_LZ : (uint32_t)k, P.bstride_z, BRICK_LZ ? (uint32_t)k << (BRICK_LX + BRICK_LY) : 0u);
+    };
+    auto tap = [&](uint32_t off) -> float { return (float)VoxelFetch<VoxelT, false>::load(vol, rs, off); };
+    // NEAREST: voxel (i, j, k), inside the volume
+    auto voxel = [&](int i, int j, int k) -> float {
+        return BIG ? fetch_voxel<VoxelT, LAYOUT>(P, vol, i, j, k) : tap(term_x(i) + term_y(j) + term_z(k));
+    };
+    // TRILINEAR at continuous voxel coordinates (u, v, w): GL's linear rule, taps clamped to the edge, x then y then z, each lerp
+    // one fma -- the isosurface kernel's sampler.  32-bit offsets fetch each x pair with one load (the generic kernel's pair loads)
+    auto trilinear = [&](float u, float v, float w) -> float {
+        const float fu = floorf(u), fv = floorf(v), fw = floorf(w);
+        const float ax = u - fu, ay = v - fv, az = w - fw;
+        const int iu = (int)fu, iv = (int)fv, iw = (int)fw;
+        const int i0 = clampi(iu, 0, P.nx - 1), i1 = clampi(iu + 1, 0, P.nx - 1);
+        const int j0 = clampi(iv, 0, P.ny - 1), j1 = clampi(iv + 1, 0, P.ny - 1);
+        const int k0 = clampi(iw, 0, P.nz - 1), k1 = clampi(iw + 1, 0, P.nz - 1);
+        float c000, c100, c010, c110, c001, c101, c011, c111;
+        if (BIG) {
+            c000 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i0, j0, k0); c100 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i1, j0, k0);
+            c010 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i0, j1, k0); c110 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i1, j1, k0);
+            c001 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i0, j0, k1); c101 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i1, j0, k1);
+            c011 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i0, j1, k1); c111 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i1, j1, k1);
+        } else {
+            const uint32_t x0 = term_x(i0), x1 = term_x(i1), y0 = term_y(j0), y1 = term_y(j1);
+            const uint32_t z0 = term_z(k0), z1 = term_z(k1);
+            const bool pair = i1 == i0 + 1 && (LAYOUT == 0 || ((uint32_t)i0 & (BRICK_X - 1u)) != BRICK_X - 1u);
+            auto tap2 = [&](uint32_t off, float &lo, float &hi) {
+                if (sizeof(VoxelT) == 1) {
+                    const uint32_t q = (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rs, (int)off, 0, 0);
+                    lo = (float)(q & 0xffu); hi = (float)(q >> 8);
+                } else {
+                    const uint32_t q = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)(off << 1), 0, 0);
+                    lo = (float)(q & 0xffffu); hi = (float)(q >> 16);
+                }
+            };
+            tap2(x0 + y0 + z0, c000, c100); tap2(x0 + y1 + z0, c010, c110);
+            tap2(x0 + y0 + z1, c001, c101); tap2(x0 + y1 + z1, c011, c111);
+            if (!pair) {
+                c100 = tap(x1 + y0 + z0); c110 = tap(x1 + y1 + z0); c101 = tap(x1 + y0 + z1); c111 = tap(x1 + y1 + z1);
+            }
+        }
+        const float c00 = tri_lerp(c000, c100, ax), c10 = tri_lerp(c010, c110, ax);
+        const float c01 = tri_lerp(c001, c101, ax), c11 = tri_lerp(c011, c111, ax);
+        const float e0 = tri_lerp(c00, c10, ay), e1 = tri_lerp(c01, c11, ay);
+        return tri_lerp(e0, e1, az);
+    };
+
+    // ---- the line: p = (o + X * du) + Y * dv per component, q_k = p + c_k * dw, c_k = (2k - (n - 1)) / 2 (exact)
+    const float X = (float)px, Y = (float)py;
+    const float pxv = (G.o[0] + X * G.du[0]) + Y * G.dv[0];
+    const float pyv = (G.o[1] + X * G.du[1]) + Y * G.dv[1];
+    const float pzv = (G.o[2] + X * G.du[2]) + Y * G.dv[2];
+    float m = MODE == 0 ? -__builtin_inff() : __builtin_inff(), acc = 0.0f;
+    uint32_t cnt = 0;
+    for (int k0 = 0; k0 < n; k0 += 4) {
+        // four positions and their inside tests; a sample outside (or past n) is sampled at voxel 0 and not taken, so the four
+        // loads need no branch of their own
+        float qx[4], qy[4], qz[4];
+        bool in[4];
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int k = k0 + j;
+            const float c = (float)(2 * k - (n - 1)) * 0.5f;
+            const float x = pxv + c * G.dw[0], y = pyv + c * G.dw[1], z = pzv + c * G.dw[2];
+            const float rx = x + 0.5f, ry = y + 0.5f, rz = z + 0.5f;
+            in[j] = k < n && rx >= 0.0f && rx < P.fdim[0] && ry >= 0.0f && ry < P.fdim[1] && rz >= 0.0f && rz < P.fdim[2];
+            any = any || in[j];
+            if (FILTER == 0) { qx[j] = in[j] ? rx : 0.0f; qy[j] = in[j] ? ry : 0.0f; qz[j] = in[j] ? rz : 0.0f; }
+            else { qx[j] = in[j] ? x : 0.0f; qy[j] = in[j] ? y : 0.0f; qz[j] = in[j] ? z : 0.0f; }
+        }
+        if (!any) continue;
+        float s[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (FILTER == 0) s[j] = voxel((int)qx[j], (int)qy[j], (int)qz[j]);        // r in [0, dim): truncation is the floor
+            else s[j] = trilinear(qx[j], qy[j], qz[j]);
+        }
+        // ---- the reduction, in increasing k
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (!in[j]) continue;
+            cnt++;
+            if (MODE == 0) { if (s[j] > m) m = s[j]; }
+            else if (MODE == 1) { if (s[j] < m) m = s[j]; }
+            else acc = acc + s[j];
+        }
+    }
+
+    float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f;
+    float out = __uint_as_float(0x7fc00000u);          // the canonical quiet NaN: no inside sample
+    if (cnt > 0) {
+        const float value = MODE == 2 ? acc / (float)cnt : m;
+        out = hu_offset ? value - 1000.0f : value;
+        // window (the composite mode's rule; max == min: 0)
+        float v = gl_min(gl_max(value, P.fmin), P.fmax);
+        if (P.fden == 0.0f) v = 0.0f;
+        else if (v <= P.fmax && v >= P.fmin) v = divmode == DIV_CERT ? div_cert(v - P.fmin, P.fden, P.rden) : (v - P.fmin) / P.fden;
+        c0 = v; c1 = v; c2 = v; c3 = 1.0f;
+        if (P.tf_len > 1) {
+            const int idx = clampi(floor_to_int_sat(v * (float)(P.tf_len - 1) + 0.5f), 0, P.tf_len - 1);
+            const float4 t = tf[idx];
+            c0 = t.x; c1 = t.y; c2 = t.z;
+        }
+    }
+    const size_t pix = (size_t)(P.fb_compact ? ly : py) * (size_t)P.img_w + (size_t)px;
+    store_pixel(P, fb, pix, c0, c1, c2, c3);
+    values[pix] = out;
+    if (spp) spp[pix] = cnt;
+}
+
+static inline unsigned reslice_padded_blocks(unsigned tiles_x, unsigned tiles_y)
+{
+    // as vr_kernels.hip: every XCD gets ceil(tiles_y / 8) tile rows' worth of slots; extras are padding
+    return ((tiles_y + 7u) / 8u) * tiles_x * 8u;
+}
+
+template <typename VoxelT, int LAYOUT, int FILTER, int MODE>
+static hipError_t launch_rs(const FrameParams &P, const LaunchConfig &L, const ResliceArgs &A, const void *vol, const float4 *tf,
+                            float4 *fb, uint32_t *spp, unsigned tiles_x, unsigned tiles_y, hipStream_t st)
+{
+    const int div = L.divmode_win == DIV_CERT ? DIV_CERT : DIV_EXACT;
+    const dim3 grid(reslice_padded_blocks(tiles_x, tiles_y)), block(256);
+    if (L.big_offsets)
+        hipLaunchKernelGGL((reslice_kernel<VoxelT, LAYOUT, FILTER, MODE, true>), grid, block, 0, st, P, A.g, A.n, div, A.hu_offset, 0u,
+                           (const VoxelT *)vol, tf, fb, spp, A.values, tiles_x, tiles_y);
+    else
+        hipLaunchKernelGGL((reslice_kernel<VoxelT, LAYOUT, FILTER, MODE, false>), grid, block, 0, st, P, A.g, A.n, div, A.hu_offset,
+                           (uint32_t)L.vol_bytes32, (const VoxelT *)vol, tf, fb, spp, A.values, tiles_x, tiles_y);
+    return hipGetLastError();
+}
+
+template <typename VoxelT, int LAYOUT, int FILTER>
+static hipError_t launch_rs_mode(const FrameParams &P, const LaunchConfig &L, const ResliceArgs &A, const void *vol, const float4 *tf,
+                                 float4 *fb, uint32_t *spp, unsigned tiles_x, unsigned tiles_y, hipStream_t st)
+{
+    if (A.mode == 0) return launch_rs<VoxelT, LAYOUT, FILTER, 0>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
+    if (A.mode == 1) return launch_rs<VoxelT, LAYOUT, FILTER, 1>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
+    return launch_rs<VoxelT, LAYOUT, FILTER, 2>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
+}
+
+template <typename VoxelT>
+static hipError_t launch_rs_type(const FrameParams &P, const LaunchConfig &L, const ResliceArgs &A, const void *vol, const float4 *tf,
+                                 float4 *fb, uint32_t *spp, hipStream_t st)
+{
+    const int rows = launch_local_rows(P);
+    const unsigned tiles_x = (unsigned)((P.img_w + 15) / 16), tiles_y = (unsigned)((rows + 15) / 16);
+    if (L.layout == 0) {
+        if (L.filter == 0) return launch_rs_mode<VoxelT, 0, 0>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
+        return launch_rs_mode<VoxelT, 0, 1>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
+    }
+    if (L.filter == 0) return launch_rs_mode<VoxelT, 1, 0>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
+    return launch_rs_mode<VoxelT, 1, 1>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
+}
+
+#define VR_RESLICE_ARGS const FrameParams &P, const LaunchConfig &L, const ResliceArgs &A, const void *vol, const float4 *tf, float4 *fb, uint32_t *spp, hipStream_t st
+#if VR_RESLICE_TU == 0 || VR_RESLICE_TU == -1
+hipError_t launch_reslice_u8(VR_RESLICE_ARGS) { return launch_rs_type<uint8_t>(P, L, A, vol, tf, fb, spp, st); }
+#endif
+#if VR_RESLICE_TU == 1 || VR_RESLICE_TU == -1
+hipError_t launch_reslice_u16(VR_RESLICE_ARGS) { return launch_rs_type<uint16_t>(P, L, A, vol, tf, fb, spp, st); }
+#endif
+
+// one empty kernel per unit: launching it makes the runtime inflate and load that unit's code object
+#if VR_RESLICE_TU >= 0
+#define VR_RESLICE_CAT2(a, b) a##b
+#define VR_RESLICE_CAT(a, b) VR_RESLICE_CAT2(a, b)
+__global__ void VR_RESLICE_CAT(warm_kernel_reslice, VR_RESLICE_TU)() {}
+hipError_t VR_RESLICE_CAT(launch_warm_reslice_tu, VR_RESLICE_TU)(hipStream_t st)
+{
+    hipLaunchKernelGGL(VR_RESLICE_CAT(warm_kernel_reslice, VR_RESLICE_TU), dim3(1), dim3(64), 0, st);
+    return hipGetLastError();
+}
+#endif
+
+// the unit of 8-bit volumes also carries the entry points
+#if VR_RESLICE_TU == 0 || VR_RESLICE_TU == -1
+#if VR_RESLICE_TU == 0
+hipError_t launch_reslice_u16(VR_RESLICE_ARGS);
+hipError_t launch_warm_reslice_tu1(hipStream_t st);
+#endif
+
+hipError_t launch_reslice(VR_RESLICE_ARGS, const char **kernel_name)
+{
+    if (kernel_name) *kernel_name = "reslice_kernel";
+    if (launch_local_rows(P) <= 0 || P.img_w <= 0) return hipSuccess;
+    if (!A.values || A.n < 1 || A.n > 1024 || A.mode < 0 || A.mode > 2) return hipErrorInvalidValue;
+    return L.bytes_per_voxel == 1 ? launch_reslice_u8(P, L, A, vol, tf, fb, spp, st) : launch_reslice_u16(P, L, A, vol, tf, fb, spp, st);
+}
+
+hipError_t launch_warm_reslice(hipStream_t st)
+{
+#if VR_RESLICE_TU == 0
+    hipError_t e = launch_warm_reslice_tu0(st);
+    if (e == hipSuccess) e = launch_warm_reslice_tu1(st);
+    return e;
+#else
+    (void)st;
+    return hipSuccess;
+#endif
+}
+#endif
+#undef VR_RESLICE_ARGS
+
+}  // namespace vr

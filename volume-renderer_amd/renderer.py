@@ -30,6 +30,8 @@ FB_RGBA32F, FB_GREYALPHA32F = 0, 1     # vr_set_framebuffer_format
 SYNTH_SPHERE_U8, SYNTH_NOISE_BALL, SYNTH_NOISE_BALL_CT = 0, 1, 2
 QUIRK_TRUNC_GRID, QUIRK_U16_OFFSET = 1, 2
 QUIRK_DEFAULT = QUIRK_U16_OFFSET
+VR_SLAB_MIP, VR_SLAB_MINIP, VR_SLAB_MEAN = 0, 1, 2     # vr_set_reslice
+_SLAB_MODES = {"mip": VR_SLAB_MIP, "minip": VR_SLAB_MINIP, "mean": VR_SLAB_MEAN}
 
 
 class VRError(RuntimeError):
@@ -119,6 +121,8 @@ def load_library() -> C.CDLL:
         "vr_set_kernel_variant": (i32, [h, i32]),
         "vr_set_isosurface": (i32, [h, i32, C.c_int32]),
         "vr_read_depth": (i32, [h, C.POINTER(f32), C.c_size_t]),
+        "vr_set_reslice": (i32, [h, i32, C.POINTER(f32), i32, i32]),
+        "vr_read_reslice_values": (i32, [h, C.POINTER(f32), C.c_size_t]),
         "vr_set_autotune": (i32, [h, i32]),
         "vr_export_choices": (i32, [h, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
         "vr_import_choices": (i32, [h, C.c_void_p, C.c_size_t, C.POINTER(i32)]),
@@ -206,6 +210,67 @@ def checksum(data: np.ndarray) -> int:
 
 def _fp(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def reslice_geometry(dims, spacing, center_mm, normal, up, pixel_mm, slab_step_mm, fb_size) -> np.ndarray:
+    """The 12 floats of vr_set_reslice (o, du, dv, dw in voxel index coordinates) for a plane through `center_mm`.
+
+    Millimetres: voxel (i, j, k)'s centre lies at (i * sx, j * sy, k * sz).  The in-plane frame is orthonormal in mm:
+    e_w = normal / |normal|, e_up = the part of `up` orthogonal to it, normalised, e_u = e_up x e_w.  Columns advance along
+    e_u and rows along e_up, each by `pixel_mm` (row 0 is the bottom of the displayed image, so `up` points up on screen);
+    slab steps advance along e_w by `slab_step_mm`.  (e_u, e_up, e_w) is right-handed.
+    `center_mm` lands on the image centre ((W - 1) / 2, (H - 1) / 2).  Dividing by the spacing gives voxel coordinates.
+    `dims` only documents the volume the plane is meant for: the geometry itself does not depend on it."""
+    sp = np.asarray(spacing, dtype=np.float64).reshape(3)
+    if len(tuple(dims)) != 3 or np.any(sp <= 0):
+        raise ValueError("reslice_geometry: dims and spacing need three entries, spacing > 0")
+    n = np.asarray(normal, dtype=np.float64).reshape(3)
+    u = np.asarray(up, dtype=np.float64).reshape(3)
+    if not np.linalg.norm(n) > 0:
+        raise ValueError("reslice_geometry: zero normal")
+    e_w = n / np.linalg.norm(n)
+    e_up = u - np.dot(u, e_w) * e_w
+    if not np.linalg.norm(e_up) > 1e-12 * max(np.linalg.norm(u), 1.0):
+        raise ValueError("reslice_geometry: `up` is parallel to the normal")
+    e_up = e_up / np.linalg.norm(e_up)
+    e_u = np.cross(e_up, e_w)
+    w, h = (int(v) for v in fb_size)
+    c = np.asarray(center_mm, dtype=np.float64).reshape(3)
+    du = float(pixel_mm) * e_u
+    dv = float(pixel_mm) * e_up
+    o = c - ((w - 1) / 2.0) * du - ((h - 1) / 2.0) * dv
+    dw = float(slab_step_mm) * e_w
+    return np.concatenate([o / sp, du / sp, dv / sp, dw / sp]).astype(np.float32)
+
+
+# axis planes: (normal axis, normal, up) -- columns along x (axial, coronal) or y (sagittal), rows along increasing y or z
+_AXIS_PLANES = {
+    "axial": (2, (0.0, 0.0, 1.0), (0.0, 1.0, 0.0)),         # columns +x, rows +y
+    "coronal": (1, (0.0, -1.0, 0.0), (0.0, 0.0, 1.0)),      # columns +x, rows +z
+    "sagittal": (0, (1.0, 0.0, 0.0), (0.0, 0.0, 1.0)),      # columns +y, rows +z
+}
+
+
+def axis_reslice(axis, index, dims, spacing, fb_size, n=1, slab_step_mm=None) -> np.ndarray:
+    """vr_set_reslice geometry of the axial (z = index), coronal (y = index) or sagittal (x = index) plane, centred on the
+    volume and scaled so that it fits the image with square pixels in mm.  `axis` is the name or the volume axis (0 = x:
+    sagittal, 1 = y: coronal, 2 = z: axial).  Slab steps default to one voxel along the normal axis.  The slab is centred on
+    the plane whatever its length, so `n` (the samples setReslice will be given) is only checked against 1..1024."""
+    if not 1 <= int(n) <= 1024:
+        raise ValueError("axis_reslice: n outside 1..1024")
+    if not isinstance(axis, str):
+        axis = {0: "sagittal", 1: "coronal", 2: "axial"}[int(axis)]
+    a, normal, up = _AXIS_PLANES[axis]
+    dims = tuple(int(v) for v in dims)
+    sp = np.asarray(spacing, dtype=np.float64).reshape(3)
+    ext = np.asarray(dims, dtype=np.float64) * sp                 # edge to edge, mm
+    cols, rows = [b for b in range(3) if b != a]
+    w, h = (int(v) for v in fb_size)
+    pixel_mm = max(ext[cols] / w, ext[rows] / h)
+    center = (np.asarray(dims, dtype=np.float64) - 1.0) / 2.0 * sp
+    center[a] = float(index) * sp[a]
+    step = sp[a] if slab_step_mm is None else float(slab_step_mm)
+    return reslice_geometry(dims, sp, center, normal, up, pixel_mm, step, fb_size)
 
 
 class RendererGroup:
@@ -513,6 +578,28 @@ class RendererCore:
         w, h = self.framebuffer_size
         out = np.zeros((h if rows is None else int(rows), w), dtype=np.float32)
         self._check(self._lib.vr_read_depth(self._h, _fp(out), out.size))
+        return out
+
+    def setReslice(self, enable, origin=None, du=None, dv=None, dw=None, mode="mip", n=1):
+        """multi-planar reslice mode: the plane o + x * du + y * dv (voxel index coordinates), a slab of n samples along dw
+        reduced by `mode` ("mip", "minip", "mean" or a VR_SLAB_* value).  `origin` may also be the 12 floats of
+        reslice_geometry() / axis_reslice() with du, dv, dw left out.  enable = False ignores the rest."""
+        if not enable:
+            self._check(self._lib.vr_set_reslice(self._h, 0, None, 0, 1))
+            return
+        if du is None and dv is None and dw is None:
+            g = np.ascontiguousarray(origin, dtype=np.float32).reshape(12)
+        else:
+            g = np.ascontiguousarray(np.concatenate([np.asarray(v, dtype=np.float32).reshape(3) for v in (origin, du, dv, dw)]))
+        m = _SLAB_MODES[mode.lower()] if isinstance(mode, str) else int(mode)
+        self._check(self._lib.vr_set_reslice(self._h, 1, _fp(g), m, int(n)))
+
+    def readResliceValues(self, rows=None) -> np.ndarray:
+        """the last reslice frame's values [rows, W] float32 (window units, HU for CT; NaN = no sample); rows = localRows()
+        for a compact target"""
+        w, h = self.framebuffer_size
+        out = np.zeros((h if rows is None else int(rows), w), dtype=np.float32)
+        self._check(self._lib.vr_read_reslice_values(self._h, _fp(out), out.size))
         return out
 
     def setKernelVariant(self, variant):
