@@ -221,6 +221,38 @@ int vr_set_reslice(vr_handle h, int enable, const float geom12[12], int slab_mod
 /* the last reslice frame's values: one float per pixel of the colour target, indexed like it (as vr_read_depth); pixels that
    frame did not render keep earlier values (NaN initially).  VR_E_INVALID before the first reslice frame. */
 int vr_read_reslice_values(vr_handle h, float *values, size_t n_floats);
+/* Gradient-lit compositing, "shade" (no reference equivalent): the composite image with each visible sample's colour lit by
+   the data's gradient and the isosurface mode's two-sided headlight.  An option of the composite mode only: with the MIP
+   switch on frames are the MIP frames bit for bit, and while the isosurface or reslice mode is on that mode renders as
+   before; the shading state is kept throughout (neither mode refuses it, it refuses neither).  Default off; initial
+   coefficients 0.15, 0.65, 0.2, shininess 16 (the isosurface mode's constants).  Per pixel, each step one correctly rounded
+   fp32 operation in the order given (nothing contracted; the only fused operations are TRILINEAR's lerps, as in the other
+   modes):
+   1. March, window, classification: exactly the composite mode's -- the ray, box entry, p0, the composite step, both
+      VR_ACCUM_* modes, the view mapping, the loop-top test including dest.a >= 0.95, max_steps, the window, the grey ramp or
+      the transfer function's index rule; then a = src.a * alpha_scale.
+   2. A sample with a != 0 is shaded (steps 3, 4).  One with a == 0 adds the same bits shaded or not (finite rgb x 0): no
+      gradient is taken for it.
+   3. Normal at the sample position q_i: the isosurface mode's step 4 with h = q_i -- NEAREST at the sample's own voxel indices
+      +- 1, TRILINEAR at the continuous coordinates u +- 1, v +- 1, w +- 1 around the sample, clamped; the view's box-space
+      mapping; N = v * (1 / sqrt(dot)); dot = 0: N = -dir.
+   4. Headlight: the isosurface mode's step 5 -- d made non-negative; spec = d^shininess by log2(shininess) squarings
+      (shininess 1: spec = d); lit = ambient + diffuse * d (the product first); per r, g, b: c' = min(c * lit + specular * spec, 1).
+   5. Compositing: exactly the composite mode's with c' in place of the classified rgb: src.rgb *= a, om = 1 - dest.a,
+      dest += src * om, and the dest.a > 0.99 break.
+   Consequences: alpha and vr_count_samples (gradient taps are not counted) are those of the unshaded composite frame;
+   (1, 0, 0, any) gives the unshaded composite frame bit for bit (LUT entries and grey values lie in [0, 1]); without a
+   transfer function r == g == b, so it is a grey mode (VR_FB_GREYALPHA32F targets, a vr_group's (grey, alpha) gather).
+   vr_set_skip_empty applies with the composite mode's dilated 8^3 cell-max grid and threshold rule (NEAREST: every value up
+   to the threshold has a == 0; TRILINEAR: the table's whole leading zero-alpha run): skipped samples have a == 0, so frames
+   and counts are the same bits either way.  Row ranges, stripes, compact and grey-alpha external targets, VR_QUIRK_TRUNC_GRID,
+   volumes beyond 32-bit offsets, vr_render_async and vr_group members apply.  A shaded frame explores, settles and evicts
+   nothing in the measured launch choices; vr_get_launch_choice is 0 after it.
+   VR_E_INVALID for a coefficient that is non-finite or < 0, or a shininess outside 1, 2, 4, ..., 128; a refused call changes
+   nothing.  enable = 0 ignores the other arguments and always succeeds. */
+int vr_set_shading(vr_handle h, int enable, float ambient, float diffuse, float specular, int shininess);
+/* the shading state (any pointer may be NULL) */
+int vr_get_shading(vr_handle h, int *enable, float *ambient, float *diffuse, float *specular, int *shininess);
 /* kernel selection: 0 = automatic (specialised kernels when the configuration allows; launches far from filling the
    chip -- fewer than 256 active 32x16 tiles, 1024 when the view is oblique to the volume axes -- use the 4-wavefront
    relay kernel; the fast kernel runs its software-pipelined batch loop unless alpha_scale >= 0.5),

@@ -17,6 +17,7 @@
 #include "volume_io.h"
 #include "vr_iso.h"
 #include "vr_reslice.h"
+#include "vr_shade.h"
 #include "vr_kernels.h"
 
 namespace vr {
@@ -170,6 +171,7 @@ bool RendererCore::loadShader(std::string fn, bool reload)
         check(launch_warm_modules(stream()), "module pre-load");
         check(launch_warm_iso(stream()), "module pre-load (isosurface)");
         check(launch_warm_reslice(stream()), "module pre-load (reslice)");
+        check(launch_warm_shade(stream()), "module pre-load (shading)");
         check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
         tslab_warm_ = false;
         if (filter == 1) warmTrilinear();
@@ -748,6 +750,23 @@ float4 *RendererCore::prepareLaunch(FrameParams &P, LaunchConfig &L)
         last_choice_ = 0;
         return fb;
     }
+    if (shadeFrame()) {
+        // the gradient-lit composite kernel (vr_shade.hip): one kernel, no measured choice (nothing explored, settled or evicted),
+        // no tile table or speed copies; the skip grid when skipping is on and some cell classifies to alpha 0 (the composite
+        // mode's threshold rule: NEAREST per value, TRILINEAR the table's whole leading zero-alpha run)
+        buildFrame(P, L);
+        P.skip_empty = 0;
+        shade_skip_grid_ = nullptr;
+        int thresh = 0;
+        if (skip_empty && zeroAlphaThreshold(P, filter == 1, thresh) && ensureSkipGrid() && thresh >= (int)skip_grid_min_) {
+            P.cnx = (int32_t)((res_dims_[0] + 7) / 8); P.cny = (int32_t)((res_dims_[1] + 7) / 8); P.cnz = (int32_t)((res_dims_[2] + 7) / 8);
+            shade_skip_grid_ = d_skip_grid_;
+            shade_skip_thresh_ = thresh;
+        }
+        tune_measure_ = false;
+        last_choice_ = 0;
+        return fb;
+    }
     if (filter == 1) warmTrilinear();          // (a caller that set the public field directly; a no-op once done)
     buildFrame(P, L);
     refreshSkipGrid(P, L);
@@ -1253,8 +1272,26 @@ void RendererCore::refreshSkipGrid(FrameParams &P, LaunchConfig &L)
         for (int a = 0; a < 3; a++) max_delta = std::max(max_delta, P.step * vdim[a] / P.ext[a]);
         if (!(4.0f * max_delta + 0.6f <= 8.0f)) return;
     }
-    // threshold: largest voxel value whose classification is exactly zero
     int thresh;
+    if (!zeroAlphaThreshold(P, staged_tri, thresh)) return;
+    const uint32_t cnx = (uint32_t)(nx + 7) / 8, cny = (uint32_t)(ny + 7) / 8, cnz = (uint32_t)(nz + 7) / 8;
+    const size_t cells = (size_t)cnx * cny * cnz;
+    if (cells * 2 >= (1ull << 32) || cnx >= (1u << 24) || (uint64_t)cny * cnz >= (1u << 24)) return;
+    if (!ensureSkipGrid()) return;
+    // nothing to skip at this threshold (a window that starts at the data's floor): the launch takes the instances without
+    // skipping -- theirs are the leaner loops (staged TRILINEAR 3.8 %, its tiles on global taps 20 %, the NEAREST kernels a
+    // workgroup of occupancy).  A host comparison against the grid's smallest cell: no device work, no synchronisation per frame.
+    if (thresh < (int)skip_grid_min_) return;
+    P.skip_empty = 1;
+    P.skip_thresh = thresh;
+    P.cnx = (int32_t)cnx; P.cny = (int32_t)cny; P.cnz = (int32_t)cnz;
+    L.skip_grid = d_skip_grid_;
+    L.skip_grid_bytes = (uint32_t)(cells * sizeof(uint16_t));
+}
+
+// threshold: largest voxel value whose classification is exactly zero
+bool RendererCore::zeroAlphaThreshold(const FrameParams &P, bool whole_run, int &thresh) const
+{
     if (P.alpha_scale == 0.0f) {
         thresh = 65535;
     } else if (tf_lut_.empty()) {
@@ -1271,24 +1308,12 @@ void RendererCore::refreshSkipGrid(FrameParams &P, LaunchConfig &L)
             const float v = (s - P.fmin) / P.fden;       // == the kernel's certified quotient
             int idx = (int)std::floor(v * 255.0f + 0.5f);
             idx = std::min(std::max(idx, 0), 255);
-            if (staged_tri ? idx >= zero_run : tf_lut_[4 * idx + 3] * P.alpha_scale != 0.0f) break;
+            if (whole_run ? idx >= zero_run : tf_lut_[4 * idx + 3] * P.alpha_scale != 0.0f) break;
         }
         thresh = u_.min_val + e - 1;                     // e == 0: even the lowest entry is visible
-        if (e == 0) return;
+        if (e == 0) return false;
     }
-    const uint32_t cnx = (uint32_t)(nx + 7) / 8, cny = (uint32_t)(ny + 7) / 8, cnz = (uint32_t)(nz + 7) / 8;
-    const size_t cells = (size_t)cnx * cny * cnz;
-    if (cells * 2 >= (1ull << 32) || cnx >= (1u << 24) || (uint64_t)cny * cnz >= (1u << 24)) return;
-    if (!ensureSkipGrid()) return;
-    // nothing to skip at this threshold (a window that starts at the data's floor): the launch takes the instances without
-    // skipping -- theirs are the leaner loops (staged TRILINEAR 3.8 %, its tiles on global taps 20 %, the NEAREST kernels a
-    // workgroup of occupancy).  A host comparison against the grid's smallest cell: no device work, no synchronisation per frame.
-    if (thresh < (int)skip_grid_min_) return;
-    P.skip_empty = 1;
-    P.skip_thresh = thresh;
-    P.cnx = (int32_t)cnx; P.cny = (int32_t)cny; P.cnz = (int32_t)cnz;
-    L.skip_grid = d_skip_grid_;
-    L.skip_grid_bytes = (uint32_t)(cells * sizeof(uint16_t));
+    return true;
 }
 
 bool RendererCore::ensureSkipGrid()
@@ -1485,6 +1510,15 @@ hipError_t RendererCore::launchKernel(const FrameParams &P, const LaunchConfig &
         A.values = d_values_;
         return launch_reslice(P, L, A, d_vol_, d_tf_, fb, spp, stream(), &last_kernel_);
     }
+    if (shadeFrame()) {
+        ShadeArgs A;
+        A.ambient = shade_k_[0]; A.diffuse = shade_k_[1]; A.specular = shade_k_[2];
+        A.spec_squarings = 0;
+        while ((1 << A.spec_squarings) < shade_shininess_) A.spec_squarings++;
+        A.skip_grid = shade_skip_grid_;
+        A.skip_thresh = shade_skip_thresh_;
+        return launch_raymarch_shade(P, L, A, d_vol_, d_tf_, fb, spp, stream(), &last_kernel_);
+    }
     if (!iso_enable_) return launch_raymarch(P, L, d_vol_, d_tf_, fb, spp, stream(), &last_kernel_);
     IsoArgs A;
     A.iso_s = isoStored();
@@ -1530,6 +1564,27 @@ void RendererCore::setReslice(bool enable, const float *geom12, int mode, int n)
     reslice_mode_ = mode;
     reslice_n_ = n;
     reslice_enable_ = true;
+}
+
+void RendererCore::setShading(bool enable, float ambient, float diffuse, float specular, int shininess)
+{
+    if (!enable) { shade_enable_ = false; return; }
+    for (float k : {ambient, diffuse, specular})
+        if (!std::isfinite(k) || k < 0.0f) throw std::invalid_argument("setShading: a coefficient is non-finite or negative");
+    if (shininess < 1 || shininess > 128 || (shininess & (shininess - 1)) != 0)
+        throw std::invalid_argument("setShading: shininess outside 1, 2, 4, ..., 128");
+    shade_k_[0] = ambient; shade_k_[1] = diffuse; shade_k_[2] = specular;
+    shade_shininess_ = shininess;
+    shade_enable_ = true;
+}
+
+void RendererCore::getShading(int *enable, float *ambient, float *diffuse, float *specular, int *shininess) const
+{
+    if (enable) *enable = shade_enable_ ? 1 : 0;
+    if (ambient) *ambient = shade_k_[0];
+    if (diffuse) *diffuse = shade_k_[1];
+    if (specular) *specular = shade_k_[2];
+    if (shininess) *shininess = shade_shininess_;
 }
 
 void RendererCore::readResliceValues(float *values, size_t n_floats)

@@ -85,7 +85,7 @@ public:
     void *framebufferDevice() const { return ext_fb_ ? ext_fb_ : d_fb_; }
     void setStream(hipStream_t s) { user_stream_ = s; }
     hipStream_t streamHandle() const { return stream(); }     // the stream the next launch goes to
-    bool greyMode() const { return tf_lut_.empty() && !iso_enable_; }   // r == g == b in every pixel (no transfer function, no isosurface; reslice frames without one are grey)
+    bool greyMode() const { return tf_lut_.empty() && !iso_enable_; }   // r == g == b in every pixel (no transfer function, no isosurface; reslice and shaded composite frames without one are grey)
     void prepareForLaunch() { FrameParams P; LaunchConfig L; (void)prepareLaunch(P, L); }   // certification, tile order, packed copy: host work a timed launch should not carry
     void setExternalFramebuffer(void *p) { ext_fb_ = p; }
     void setRowRange(int b, int e) { row_begin_ = b; row_end_ = e; }
@@ -127,6 +127,11 @@ public:
     void setReslice(bool enable, const float *geom12, int mode, int n);
     bool resliceEnabled() const { return reslice_enable_; }
     void readResliceValues(float *values, size_t n_floats);   // the last reslice frame's values target (as readDepth)
+    // gradient-lit compositing (vr_set_shading): an option of the composite mode -- MIP, isosurface and reslice frames ignore it
+    // and keep it.  enable = false ignores the other arguments; a coefficient that is non-finite or < 0, or a shininess outside
+    // 1, 2, 4, ..., 128: std::invalid_argument, the state unchanged
+    void setShading(bool enable, float ambient, float diffuse, float specular, int shininess);
+    void getShading(int *enable, float *ambient, float *diffuse, float *specular, int *shininess) const;
 
     int filter = 0, accum = 0, skip_empty = 0;
     int layout = 1;          // VR_LAYOUT_BRICKED: the faster HBM layout is the default (vr_set_layout)
@@ -181,6 +186,10 @@ private:
     float *d_values_ = nullptr;              // values target of the reslice frames (NaN where no sample; allocated on the first one)
     size_t values_capacity_ = 0;             // floats
     int values_rows_ = -1, values_w_ = 0;    // rows x width the last reslice frame's values are indexed by (-1: no reslice frame yet)
+    bool shade_enable_ = false;
+    float shade_k_[3] = {0.15f, 0.65f, 0.2f};   // ambient, diffuse, specular (the isosurface mode's constants)
+    int shade_shininess_ = 16;
+    bool shadeFrame() const { return shade_enable_ && !iso_enable_ && !reslice_enable_ && u_.is_MIP != 1; }   // the next frame is a shaded composite one
     int stripe_rows_ = 0, stripe_index_ = 0, stripe_count_ = 1;
     bool fb_compact_ = false;
     int fb_format_ = 0;
@@ -217,7 +226,13 @@ private:
     void refuseIsoGreyAlpha() const;
     bool ensureSkipGrid();                   // build the dilated cell-max grid if it is not resident; false = the volume is too large for it
     const uint16_t *iso_skip_grid_ = nullptr;   // the grid the iso launch being prepared skips on (nullptr = no skipping)
-    hipError_t launchKernel(const FrameParams &P, const LaunchConfig &L, float4 *fb, uint32_t *spp);   // the ray-march, the iso or the reslice kernel
+    // the largest stored value every sample at or below which classifies to alpha exactly 0 (composite mode, this frame's window,
+    // transfer function and alpha_scale); whole_run: the table's whole leading zero-alpha run must lie beyond it (TRILINEAR, whose
+    // values fall between the integers).  false: even the lowest value is visible
+    bool zeroAlphaThreshold(const FrameParams &P, bool whole_run, int &thresh) const;
+    const uint16_t *shade_skip_grid_ = nullptr;   // the grid the shaded launch being prepared skips on (nullptr = no skipping) ...
+    int shade_skip_thresh_ = 0;                   // ... and its threshold
+    hipError_t launchKernel(const FrameParams &P, const LaunchConfig &L, float4 *fb, uint32_t *spp);   // the ray-march, the iso, the reslice or the shaded kernel
     uint32_t *d_tile_table_ = nullptr;       // work-ordered block -> tile table (tile_schedule.h)
     size_t tile_table_capacity_ = 0, tile_table_blocks_ = 0;
     uint32_t *d_tile_table_tall_ = nullptr;  // the same for 16x32-pixel tiles (the staged trilinear kernel's tall shape); built with the table above

@@ -341,6 +341,18 @@ int vr_read_reslice_values(vr_handle h, float *values, size_t n_floats)
     return guarded(h, [&](vr::RendererCore &c) { c.readResliceValues(values, n_floats); });
 }
 
+int vr_set_shading(vr_handle h, int enable, float ambient, float diffuse, float specular, int shininess)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.setShading(enable != 0, ambient, diffuse, specular, shininess); });
+}
+
+int vr_get_shading(vr_handle h, int *enable, float *ambient, float *diffuse, float *specular, int *shininess)
+{
+    if (!h) return VR_E_INVALID;
+    h->core.getShading(enable, ambient, diffuse, specular, shininess);
+    return VR_OK;
+}
+
 int vr_set_autotune(vr_handle h, int enable)
 {
     if (!h) return VR_E_INVALID;

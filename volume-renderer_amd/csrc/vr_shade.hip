@@ -1,0 +1,331 @@
+// vr_shade.hip -- the gradient-lit composite kernel (vr_set_shading): the composite mode's march, window, classification and
+// compositing, with each visible sample's colour lit by a central-difference normal and the isosurface mode's two-sided
+// headlight.  The definition, step by step, is in include/vr_core.h and DESIGN.md section 1.3; tests/shade_ref/shade_ref.c
+// restates it on the CPU and tests/test_shading_gpu.py holds this kernel to it bit for bit.
+//
+// Its own translation units (VR_SHADE_TU = 0: 8-bit volumes, 1: 16-bit volumes), like vr_iso.hip: the vr_kernels.hip units,
+// FrameParams and LaunchConfig are untouched by the mode; the coefficients and the skip grid are extra kernel arguments.
+// Arithmetic contract as in vr_kernels.hip: one correctly rounded fp32 operation per step, nothing contracted
+// (-ffp-contract=off), the only fused operations are explicit: TRILINEAR's lerps (tri_lerp) and the certified divisions
+// (div_cert: texture coordinates and the window).
+//
+// Shape: the isosurface kernel's -- one pixel per lane, 8x8 pixels per wavefront, 16x16-pixel tiles of four wavefronts dealt to
+// the XCDs by tile_of_block().  The 256-entry transfer function is staged in LDS (4 KiB): every sample reads one entry.
+// Samples with alpha 0 take no gradient (their contribution is finite rgb x 0 either way).  NEAREST gradients are six voxel
+// loads around the sample's voxel; TRILINEAR gradients are six sampler evaluations, each with its own floor and taps: in fp32
+// floor(u + 1) is not always floor(u) + 1, so taps are not shared between them.
+// Empty-space skipping per 8^3 cell: a sample's taps lie within one voxel of its NEAREST voxel (TRILINEAR: of its lower tap),
+// so a sample in a cell whose DILATED maximum is <= the threshold (RendererCore::zeroAlphaThreshold) classifies to alpha 0 and
+// is not fetched: it would add +-0 to dest, which is never -0.  Positions still advance sample by sample and every step is
+// counted, so frames and counts are the same bits with and without it.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "vr_device.h"
+#include "vr_shade.h"
+
+#ifndef VR_SHADE_TU
+#define VR_SHADE_TU -1
+#endif
+
+namespace vr {
+
+template <typename VoxelT, int LAYOUT, int FILTER, bool SKIP, bool BIG>
+__global__ __launch_bounds__(256) void raymarch_shade_kernel(const FrameParams P, const int divmode, const int divmode_win,
+                                                             const uint32_t vol_bytes, const VoxelT *__restrict__ vol,
+                                                             const float4 *__restrict__ tf, float4 *__restrict__ fb,
+                                                             uint32_t *__restrict__ spp, const uint16_t *__restrict__ grid,
+                                                             const int32_t skip_thresh, const float k_amb, const float k_dif,
+                                                             const float k_spec, const int spec_squarings, const unsigned tiles_x,
+                                                             const unsigned tiles_y)
+{
+    __shared__ float4 s_tf[256];
+    unsigned tx, ty;
+    tile_of_block(blockIdx.x, tiles_x, tiles_y, tx, ty);
+    if (tx == 0xffffffffu) return;                 // (a padding block: all of its threads)
+    const bool use_tf = P.tf_len > 1;              // (the launcher refuses tf_len > 256)
+    if (use_tf && (int)threadIdx.x < P.tf_len) s_tf[threadIdx.x] = tf[threadIdx.x];
+    __syncthreads();
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const int lx = (int)(tx * 16u + (wave & 1u) * 8u + (lane & 7u));
+    const int ly = (int)(ty * 16u + (wave >> 1) * 8u + (lane >> 3));
+    int px = lx, py;
+    if (P.stripe_count > 1) {
+        const int s = ly / P.stripe_rows, r = ly % P.stripe_rows;
+        py = (s * P.stripe_count + P.stripe_index) * P.stripe_rows + r;
+    } else {
+        py = P.row_begin + ly;
+    }
+    if (px >= P.col_lim || py >= P.row_lim || py >= P.row_end) return;
+
+    const Ray ray = compute_ray(P, (float)px + 0.5f, (float)py + 0.5f);
+    float t_min = 0.0f, t_max = 0.0f;
+    float d0 = 0.0f, d1 = 0.0f, d2 = 0.0f, d3 = 0.0f;
+    uint32_t fetches = 0;
+    if (intersect_ray_aabb(P, ray, t_min, t_max)) {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)vol, 0, BIG ? 0 : (int)pair_load_extent(vol_bytes), 0x00020000);
+        // per-axis terms of VoxelAddr<LAYOUT, false>::at(i, j, k) = X(i) + Y(j) + Z(k)  (mod 2^32), as in the generic kernel
+        auto term_x = [&](int i) -> uint32_t {
+            return LAYOUT == 0 ? (uint32_t)i : mad_u24((uint32_t)i >> BRICK_LX, 64u - (uint32_t)BRICK_X, (uint32_t)i);
+        };
+        auto term_y = [&](int j) -> uint32_t {
+            if (LAYOUT == 0) return mad_u24((uint32_t)j, (uint32_t)P.nx, 0u);
+            return mad_u24(BRICK_LY ? (uint32_t)j >> BRICK_LY : (uint32_t)j, P.bstride_y, BRICK_LY ? (uint32_t)j << BRICK_LX : 0u);
+        };
+        auto term_z = [&](int k) -> uint32_t {
+            if (LAYOUT == 0) return mad_u24(mad_u24((uint32_t)k, (uint32_t)P.ny, 0u), (uint32_t)P.nx, 0u);
+            return mad_u24(BRICK_LZ ? (uint32_t)k >> BRICK_LZ : (uint32_t)k, P.bstride_z, BRICK_LZ ? (uint32_t)k << (BRICK_LX + BRICK_LY) : 0u);
+        };
+        auto tap = [&](uint32_t off) -> float { return (float)VoxelFetch<VoxelT, false>::load(vol, rs, off); };
+        // NEAREST: voxel (i, j, k), indices already clamped
+        auto voxel = [&](int i, int j, int k) -> float {
+            return BIG ? fetch_voxel<VoxelT, LAYOUT>(P, vol, i, j, k) : tap(term_x(i) + term_y(j) + term_z(k));
+        };
+        // TRILINEAR at the sampler's own continuous coordinates (u, v, w) = tc * dim - 0.5: GL's linear rule, taps clamped to
+        // the edge, x then y then z, each lerp one fma.  32-bit offsets fetch each x pair with one load (the generic kernel's pair loads)
+        auto trilinear = [&](float u, float v, float w) -> float {
+            const float fu = floorf(u), fv = floorf(v), fw = floorf(w);
+            const float ax = u - fu, ay = v - fv, az = w - fw;
+            const int iu = (int)fu, iv = (int)fv, iw = (int)fw;
+            const int i0 = clampi(iu, 0, P.nx - 1), i1 = clampi(iu + 1, 0, P.nx - 1);
+            const int j0 = clampi(iv, 0, P.ny - 1), j1 = clampi(iv + 1, 0, P.ny - 1);
+            const int k0 = clampi(iw, 0, P.nz - 1), k1 = clampi(iw + 1, 0, P.nz - 1);
+            float c000, c100, c010, c110, c001, c101, c011, c111;
+            if (BIG) {
+                c000 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i0, j0, k0); c100 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i1, j0, k0);
+                c010 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i0, j1, k0); c110 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i1, j1, k0);
+                c001 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i0, j0, k1); c101 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i1, j0, k1);
+                c011 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i0, j1, k1); c111 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i1, j1, k1);
+            } else {
+                const uint32_t x0 = term_x(i0), x1 = term_x(i1), y0 = term_y(j0), y1 = term_y(j1);
+                const uint32_t z0 = term_z(k0), z1 = term_z(k1);
+                const bool pair = i1 == i0 + 1 && (LAYOUT == 0 || ((uint32_t)i0 & (BRICK_X - 1u)) != BRICK_X - 1u);
+                auto tap2 = [&](uint32_t off, float &lo, float &hi) {
+                    if (sizeof(VoxelT) == 1) {
+                        const uint32_t q = (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rs, (int)off, 0, 0);
+                        lo = (float)(q & 0xffu); hi = (float)(q >> 8);
+                    } else {
+                        const uint32_t q = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)(off << 1), 0, 0);
+                        lo = (float)(q & 0xffffu); hi = (float)(q >> 16);
+                    }
+                };
+                tap2(x0 + y0 + z0, c000, c100); tap2(x0 + y1 + z0, c010, c110);
+                tap2(x0 + y0 + z1, c001, c101); tap2(x0 + y1 + z1, c011, c111);
+                if (!pair) {
+                    c100 = tap(x1 + y0 + z0); c110 = tap(x1 + y1 + z0); c101 = tap(x1 + y0 + z1); c111 = tap(x1 + y1 + z1);
+                }
+            }
+            const float c00 = tri_lerp(c000, c100, ax), c10 = tri_lerp(c010, c110, ax);
+            const float c01 = tri_lerp(c001, c101, ax), c11 = tri_lerp(c011, c111, ax);
+            const float e0 = tri_lerp(c00, c10, ay), e1 = tri_lerp(c01, c11, ay);
+            return tri_lerp(e0, e1, az);
+        };
+        auto nearest_index = [&](float tc, float fdim, int n) -> int { return clampi(floor_to_int_sat(tc * fdim), 0, n - 1); };
+
+        const float EPSILON = 0.000001f;
+        const float sx = ray.ox + ray.dx * t_min, sy = ray.oy + ray.dy * t_min, sz = ray.oz + ray.dz * t_min;
+        const float p0x = sx + ray.dx * EPSILON, p0y = sy + ray.dy * EPSILON, p0z = sz + ray.dz * EPSILON;
+        const float dsx = ray.dx * P.step, dsy = ray.dy * P.step, dsz = ray.dz * P.step;
+        // the headlight L = V = H = -dir, and the box-space scale of each volume axis (dim / ext, the view's permutation)
+        const float lx_ = -ray.dx, ly_ = -ray.dy, lz_ = -ray.dz;
+        const float gsx = P.fdim[0] / P.ext[0];
+        const float gsy = (P.view_top == 1 || P.view_bottom == 1) ? P.fdim[2] / P.ext[1] : P.fdim[1] / P.ext[1];
+        const float gsz = (P.view_top == 1 || P.view_bottom == 1) ? P.fdim[1] / P.ext[2] : P.fdim[2] / P.ext[2];
+        float qx = p0x, qy = p0y, qz = p0z;
+        uint32_t cell = 0xffffffffu;
+        bool cell_empty = false;
+        for (int i = 0; i < P.max_steps; i++) {
+            if (P.accum == 1) {
+                const float fi = (float)i;
+                qx = p0x + fi * dsx; qy = p0y + fi * dsy; qz = p0z + fi * dsz;
+            }
+            // cartesianToTextureCoord (VolumeRenderer.cs:175-192), as the generic kernel computes it
+            float ux = qx + P.half[0], uy = qy + P.half[1], uz = qz + P.half[2];
+            if (divmode == DIV_CERT) {
+                ux = div_cert(ux, P.ext[0], P.rext[0]);
+                uy = div_cert(uy, P.ext[1], P.rext[1]);
+                uz = div_cert(uz, P.ext[2], P.rext[2]);
+            } else {
+                ux = ux / P.ext[0]; uy = uy / P.ext[1]; uz = uz / P.ext[2];
+            }
+            const float uzr = uz;
+            uz = 1.0f - uz;
+            float tcx, tcy, tcz;
+            if (P.view_top == 1) { tcx = ux; tcy = uzr; tcz = uy; }
+            else if (P.view_bottom == 1) { tcx = ux; tcy = uz; tcz = 1.0f - uy; }
+            else { tcx = ux; tcy = uy; tcz = uz; }
+            if (tcx > 1.0f || tcy > 1.0f || tcz > 1.0f || tcx < 0.0f || tcy < 0.0f || tcz < 0.0f || d3 >= 0.95f) break;
+            fetches++;
+            // the sample's voxel (NEAREST) or its lower tap and continuous coordinates (TRILINEAR)
+            int vi, vj, vk;
+            float u = 0.0f, v = 0.0f, w = 0.0f;
+            if (FILTER == 0) {
+                vi = nearest_index(tcx, P.fdim[0], P.nx); vj = nearest_index(tcy, P.fdim[1], P.ny); vk = nearest_index(tcz, P.fdim[2], P.nz);
+            } else {
+                u = tcx * P.fdim[0] - 0.5f; v = tcy * P.fdim[1] - 0.5f; w = tcz * P.fdim[2] - 0.5f;
+                vi = clampi((int)floorf(u), 0, P.nx - 1); vj = clampi((int)floorf(v), 0, P.ny - 1); vk = clampi((int)floorf(w), 0, P.nz - 1);
+            }
+            bool visible = true;
+            if (SKIP) {
+                const uint32_t c = ((uint32_t)vi >> 3) + (uint32_t)P.cnx * (((uint32_t)vj >> 3) + (uint32_t)P.cny * ((uint32_t)vk >> 3));
+                if (c != cell) {
+                    cell = c;
+                    cell_empty = (int32_t)grid[c] <= skip_thresh;
+                }
+                visible = !cell_empty;
+            }
+            if (visible) {
+                float s = FILTER == 0 ? voxel(vi, vj, vk) : trilinear(u, v, w);
+                // window (VolumeRenderer.cs:122-124; Q4: max == min defined as 0), the division certified like the composite kernels'
+                s = gl_min(gl_max(s, P.fmin), P.fmax);
+                if (P.fden == 0.0f) s = 0.0f;
+                else if (s <= P.fmax && s >= P.fmin) s = divmode_win == DIV_CERT ? div_cert(s - P.fmin, P.fden, P.rden) : (s - P.fmin) / P.fden;
+                float c0 = s, c1 = s, c2 = s, a = s;
+                if (use_tf) {
+                    const int idx = clampi(floor_to_int_sat(s * (float)(P.tf_len - 1) + 0.5f), 0, P.tf_len - 1);
+                    const float4 t = s_tf[idx];
+                    c0 = t.x; c1 = t.y; c2 = t.z; a = t.w;
+                }
+                a *= P.alpha_scale;
+                if (a != 0.0f) {
+                    // ---- gradient: central differences of the same sampler at the sample, +-1 voxel per volume axis, clamped
+                    float gx, gy, gz;
+                    if (FILTER == 0) {
+                        gx = voxel(clampi(vi + 1, 0, P.nx - 1), vj, vk) - voxel(clampi(vi - 1, 0, P.nx - 1), vj, vk);
+                        gy = voxel(vi, clampi(vj + 1, 0, P.ny - 1), vk) - voxel(vi, clampi(vj - 1, 0, P.ny - 1), vk);
+                        gz = voxel(vi, vj, clampi(vk + 1, 0, P.nz - 1)) - voxel(vi, vj, clampi(vk - 1, 0, P.nz - 1));
+                    } else {
+                        gx = trilinear(u + 1.0f, v, w) - trilinear(u - 1.0f, v, w);
+                        gy = trilinear(u, v + 1.0f, w) - trilinear(u, v - 1.0f, w);
+                        gz = trilinear(u, v, w + 1.0f) - trilinear(u, v, w - 1.0f);
+                    }
+                    // volume axes -> box axes: the view's permutation, the z flip, dim / ext per axis
+                    const float Gx = gx * gsx;
+                    float Gy, Gz;
+                    if (P.view_top == 1) { Gy = gz * gsy; Gz = gy * gsz; }
+                    else if (P.view_bottom == 1) { Gy = -(gz * gsy); Gz = -(gy * gsz); }
+                    else { Gy = gy * gsy; Gz = -(gz * gsz); }
+                    // N = normalize(-G) = v * (1 / sqrt(dot)), dot summed from the last component to the first; G = 0: N = -dir
+                    float nx = -Gx, ny = -Gy, nz = -Gz;
+                    const float dot = (nz * nz + ny * ny) + nx * nx;
+                    if (dot == 0.0f) {
+                        nx = lx_; ny = ly_; nz = lz_;
+                    } else {
+                        const float rn = 1.0f / sqrtf(dot);
+                        nx = nx * rn; ny = ny * rn; nz = nz * rn;
+                    }
+                    // ---- two-sided headlight
+                    float d = (nz * lz_ + ny * ly_) + nx * lx_;
+                    if (d < 0.0f) d = -d;
+                    float spec = d;
+                    for (int k = 0; k < spec_squarings; k++) spec = spec * spec;
+                    const float lit = k_amb + k_dif * d, hl = k_spec * spec;
+                    c0 = gl_min(c0 * lit + hl, 1.0f);
+                    c1 = gl_min(c1 * lit + hl, 1.0f);
+                    c2 = gl_min(c2 * lit + hl, 1.0f);
+                }
+                // ---- compositing (VolumeRenderer.cs:130-135)
+                c0 *= a; c1 *= a; c2 *= a;
+                const float om = 1.0f - d3;
+                d0 += c0 * om; d1 += c1 * om; d2 += c2 * om; d3 += a * om;
+                if (d3 > 0.99f) break;
+            }
+            if (P.accum == 0) { qx += dsx; qy += dsy; qz += dsz; }
+        }
+    }
+    const size_t pix = (size_t)(P.fb_compact ? ly : py) * (size_t)P.img_w + (size_t)px;
+    store_pixel(P, fb, pix, d0, d1, d2, d3);
+    if (spp) spp[pix] = fetches;
+}
+
+static inline unsigned shade_padded_blocks(unsigned tiles_x, unsigned tiles_y)
+{
+    // as vr_kernels.hip: every XCD gets ceil(tiles_y / 8) tile rows' worth of slots; extras are padding
+    return ((tiles_y + 7u) / 8u) * tiles_x * 8u;
+}
+
+template <typename VoxelT, int LAYOUT, int FILTER, bool SKIP>
+static hipError_t launch_shade(const FrameParams &P, const LaunchConfig &L, const ShadeArgs &A, const void *vol, const float4 *tf,
+                               float4 *fb, uint32_t *spp, unsigned tiles_x, unsigned tiles_y, hipStream_t st)
+{
+    const int div = L.divmode_tc == DIV_EXACT ? DIV_EXACT : DIV_CERT;
+    const int div_win = L.divmode_win == DIV_CERT ? DIV_CERT : DIV_EXACT;
+    const dim3 grid(shade_padded_blocks(tiles_x, tiles_y)), block(256);
+    if (L.big_offsets)
+        hipLaunchKernelGGL((raymarch_shade_kernel<VoxelT, LAYOUT, FILTER, SKIP, true>), grid, block, 0, st, P, div, div_win, 0u,
+                           (const VoxelT *)vol, tf, fb, spp, A.skip_grid, A.skip_thresh, A.ambient, A.diffuse, A.specular,
+                           A.spec_squarings, tiles_x, tiles_y);
+    else
+        hipLaunchKernelGGL((raymarch_shade_kernel<VoxelT, LAYOUT, FILTER, SKIP, false>), grid, block, 0, st, P, div, div_win,
+                           (uint32_t)L.vol_bytes32, (const VoxelT *)vol, tf, fb, spp, A.skip_grid, A.skip_thresh, A.ambient, A.diffuse,
+                           A.specular, A.spec_squarings, tiles_x, tiles_y);
+    return hipGetLastError();
+}
+
+template <typename VoxelT>
+static hipError_t launch_shade_type(const FrameParams &P, const LaunchConfig &L, const ShadeArgs &A, const void *vol, const float4 *tf,
+                                    float4 *fb, uint32_t *spp, hipStream_t st)
+{
+    const int rows = launch_local_rows(P);
+    const unsigned tiles_x = (unsigned)((P.img_w + 15) / 16), tiles_y = (unsigned)((rows + 15) / 16);
+    const bool skip = A.skip_grid != nullptr;
+#define VR_SHADE_L(LAY)                                                                                                            \
+    if (L.filter == 0) return skip ? launch_shade<VoxelT, LAY, 0, true>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st)           \
+                                   : launch_shade<VoxelT, LAY, 0, false>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);         \
+    return skip ? launch_shade<VoxelT, LAY, 1, true>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st)                              \
+                : launch_shade<VoxelT, LAY, 1, false>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
+    if (L.layout == 0) { VR_SHADE_L(0) }
+    VR_SHADE_L(1)
+#undef VR_SHADE_L
+}
+
+#define VR_SHADE_ARGS const FrameParams &P, const LaunchConfig &L, const ShadeArgs &A, const void *vol, const float4 *tf, float4 *fb, uint32_t *spp, hipStream_t st
+#if VR_SHADE_TU == 0 || VR_SHADE_TU == -1
+hipError_t launch_shade_u8(VR_SHADE_ARGS) { return launch_shade_type<uint8_t>(P, L, A, vol, tf, fb, spp, st); }
+#endif
+#if VR_SHADE_TU == 1 || VR_SHADE_TU == -1
+hipError_t launch_shade_u16(VR_SHADE_ARGS) { return launch_shade_type<uint16_t>(P, L, A, vol, tf, fb, spp, st); }
+#endif
+
+// one empty kernel per unit: launching it makes the runtime inflate and load that unit's code object
+#if VR_SHADE_TU >= 0
+#define VR_SHADE_CAT2(a, b) a##b
+#define VR_SHADE_CAT(a, b) VR_SHADE_CAT2(a, b)
+__global__ void VR_SHADE_CAT(warm_kernel_shade, VR_SHADE_TU)() {}
+hipError_t VR_SHADE_CAT(launch_warm_shade_tu, VR_SHADE_TU)(hipStream_t st)
+{
+    hipLaunchKernelGGL(VR_SHADE_CAT(warm_kernel_shade, VR_SHADE_TU), dim3(1), dim3(64), 0, st);
+    return hipGetLastError();
+}
+#endif
+
+// the unit of 8-bit volumes also carries the entry points
+#if VR_SHADE_TU == 0 || VR_SHADE_TU == -1
+#if VR_SHADE_TU == 0
+hipError_t launch_shade_u16(VR_SHADE_ARGS);
+hipError_t launch_warm_shade_tu1(hipStream_t st);
+#endif
+
+hipError_t launch_raymarch_shade(VR_SHADE_ARGS, const char **kernel_name)
+{
+    if (kernel_name) *kernel_name = "raymarch_shade_kernel";
+    if (launch_local_rows(P) <= 0 || P.img_w <= 0) return hipSuccess;
+    if (P.tf_len > 256 || (P.tf_len > 1 && !tf) || A.spec_squarings < 0 || A.spec_squarings > 7) return hipErrorInvalidValue;
+    return L.bytes_per_voxel == 1 ? launch_shade_u8(P, L, A, vol, tf, fb, spp, st) : launch_shade_u16(P, L, A, vol, tf, fb, spp, st);
+}
+
+hipError_t launch_warm_shade(hipStream_t st)
+{
+#if VR_SHADE_TU == 0
+    hipError_t e = launch_warm_shade_tu0(st);
+    if (e == hipSuccess) e = launch_warm_shade_tu1(st);
+    return e;
+#else
+    (void)st;
+    return hipSuccess;
+#endif
+}
+#endif
+#undef VR_SHADE_ARGS
+
+}  // namespace vr

@@ -123,6 +123,8 @@ def load_library() -> C.CDLL:
         "vr_read_depth": (i32, [h, C.POINTER(f32), C.c_size_t]),
         "vr_set_reslice": (i32, [h, i32, C.POINTER(f32), i32, i32]),
         "vr_read_reslice_values": (i32, [h, C.POINTER(f32), C.c_size_t]),
+        "vr_set_shading": (i32, [h, i32, f32, f32, f32, i32]),
+        "vr_get_shading": (i32, [h, C.POINTER(i32), C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), C.POINTER(i32)]),
         "vr_set_autotune": (i32, [h, i32]),
         "vr_export_choices": (i32, [h, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
         "vr_import_choices": (i32, [h, C.c_void_p, C.c_size_t, C.POINTER(i32)]),
@@ -601,6 +603,18 @@ class RendererCore:
         out = np.zeros((h if rows is None else int(rows), w), dtype=np.float32)
         self._check(self._lib.vr_read_reslice_values(self._h, _fp(out), out.size))
         return out
+
+    def setShading(self, enable, ambient=0.15, diffuse=0.65, specular=0.2, shininess=16):
+        """gradient-lit compositing: an option of the composite mode (MIP, isosurface and reslice frames ignore it and keep it).
+        shininess in 1, 2, 4, ..., 128; enable = False ignores the rest"""
+        self._check(self._lib.vr_set_shading(self._h, int(bool(enable)), float(ambient), float(diffuse), float(specular), int(shininess)))
+
+    def shading(self) -> dict:
+        """the shading state: enable, ambient, diffuse, specular, shininess"""
+        e, n = C.c_int32(0), C.c_int32(0)
+        a, d, s = C.c_float(0.0), C.c_float(0.0), C.c_float(0.0)
+        self._check(self._lib.vr_get_shading(self._h, C.byref(e), C.byref(a), C.byref(d), C.byref(s), C.byref(n)))
+        return dict(enable=bool(e.value), ambient=a.value, diffuse=d.value, specular=s.value, shininess=int(n.value))
 
     def setKernelVariant(self, variant):
         self._check(self._lib.vr_set_kernel_variant(self._h, variant))
