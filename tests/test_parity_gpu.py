@@ -5,10 +5,18 @@ stricter -- identical fp32 operation order -- so these tests ALSO assert bit-exa
 frames and identical per-pixel fetch counts; TOL is the fallback bar quoted in
 messages.  Everything here calls libvr_core.so; the oracle is only the checker.
 """
+import importlib.util
+from pathlib import Path
+
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
+
+_spec = importlib.util.spec_from_file_location("edge_cases", Path(__file__).resolve().parent / "edge_cases.py")
+edge_cases = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(edge_cases)
+_random_camera_block = edge_cases.random_camera_block       # shared with tests/test_mode_edges_{cpu,gpu}.py
 
 TOL = 1e-4
 FAST_KERNELS = ("raymarch_fast_kernel", "raymarch_relay_kernel")   # relay = sparse launches
@@ -590,22 +598,6 @@ def test_skip_empty_full_size_windowed(vra, oracle, cfg3):
     assert total == 480301385                       # logical samples are unchanged
     print(f"cfg3 window [64,4095]: {t_plain:.3f} ms without, {t_skip:.3f} ms with empty-space skipping")
     assert t_skip < t_plain
-
-
-def _random_camera_block(rng, radius_lo=0.2, radius_hi=4.0):
-    """random eye + orthonormal basis looking roughly at the box (also from inside / grazing)"""
-    d = rng.normal(size=3); d /= np.linalg.norm(d)
-    eye = d * rng.uniform(radius_lo, radius_hi)
-    target = rng.uniform(-0.45, 0.45, size=3)
-    look = target - eye; look /= np.linalg.norm(look)
-    up0 = rng.normal(size=3)
-    side = np.cross(look, up0); side /= np.linalg.norm(side)
-    up = np.cross(side, look)
-    b = np.zeros(21, dtype=np.float32)
-    b[0:3] = side; b[4:7] = up; b[8:11] = -look; b[12:15] = eye; b[15] = 1
-    b[16:19] = eye; b[19] = 1
-    b[20] = rng.uniform(1.0, 5.0)          # view_plane_dist (FOV 22..90 degrees)
-    return b
 
 
 def test_packed12_copy_is_lossless_and_only_used_when_the_data_allow(vra, oracle):
