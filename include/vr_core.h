@@ -253,6 +253,49 @@ int vr_read_reslice_values(vr_handle h, float *values, size_t n_floats);
 int vr_set_shading(vr_handle h, int enable, float ambient, float diffuse, float specular, int shininess);
 /* the shading state (any pointer may be NULL) */
 int vr_get_shading(vr_handle h, int *enable, float *ambient, float *diffuse, float *specular, int *shininess);
+/* Gaussian smoothing of the resident volume, computed on the device (no reference equivalent; the step VTK, ParaView and
+   3D Slicer put in front of surface extraction and shading): the isosurface normal, the shading gradient and the resliced
+   values are differences of neighbouring voxels, which voxel noise dominates.  Separable, one sigma per volume axis in
+   voxels (x the fastest axis).  Each step is one correctly rounded operation in the order given:
+   1. Source: always the volume AS LOADED, never an earlier smoothing result, so a sigma slider does not accumulate.  While a
+      smoothed volume is in use the handle keeps the loaded one resident beside it.  (0, 0, 0) drops the smoothed volume and
+      renders the loaded one again, bit for bit as before the first call.  Loading, generating or reading a new volume
+      resets the state to (0, 0, 0).
+   2. Arguments: each sigma finite and 0 <= sigma <= 8; anything else is VR_E_INVALID and changes nothing.  sigma_a == 0: no
+      pass along axis a (the exact identity).  Without a volume: VR_E_INVALID (as vr_read_volume); a host-only handle:
+      VR_E_NO_DEVICE; a device allocation that fails: VR_E_NOMEM, and the handle keeps rendering what it rendered before.
+   3. Weights (vr_smooth_weights computes them, for the kernels' host side too): r = ceil(3 * sigma), at most 24;
+      g_t = exp(-t*t / (2 * sigma*sigma)) in double for t = -r .. r; sum = their sum in double, in increasing t;
+      w_t = (float)(g_t / sum).  *radius = r (may be NULL) and 2r + 1 floats are written; capacity < 2r + 1, a NULL w or a
+      sigma outside (0, 8]: VR_E_INVALID.
+   4. One pass along axis a over fp32 input `in`: acc = 0.0f; for t = -r .. r in increasing order
+      acc = acc + w_t * in[clamp(i_a + t, 0, dim_a - 1)] -- the product rounded, then the sum, nothing contracted into an fma.
+      Edges clamp, like the sampler.
+   5. Order: x, then y, then z.  The first pass reads (float)voxel; intermediates stay fp32, with no rounding to integers
+      between passes.
+   6. Store: v = the last pass's fp32 value rounded half to even, clamped to [0, 255] or [0, 65535], in the loaded volume's
+      type and layout.
+   Kept: the window (vr_get_window), the camera, view, filter, transfer function, the modes and the launch stream; no message
+   is queued.  vr_get_dataset_range, vr_histogram, vr_read_volume and vr_measure_stream_read report the volume being
+   rendered, i.e. the smoothed one; vr_get_dims is unchanged.  Everything derived from voxel values is rebuilt or invalidated
+   as a fresh load leaves it: the exact range that gates the 12-bit packed copy, that copy and every apron copy, the skip
+   grid and its minimum, the tile order under skipping (the measured launch choices are keyed by the configuration, never by
+   voxel values: a load keeps them and so does this call; whichever candidate runs, the frame is the same bits).  The
+   smoothed volume has the loaded one's storage (zeroed brick padding, the slack slab).  vr_set_layout afterwards re-lays
+   out both volumes and does not recompute the smoothing.  In vr_get_resident_bytes `volume` is the rendered volume and the
+   kept loaded one counts under `other`: it is not an optional copy and vr_set_copy_budget never frees it.  Members of a
+   vr_group are ordinary handles: smooth every member with the same values.
+   Intermediates are fp32 planes on the device, freed before the call returns: the whole volume's where one buffer fits
+   the workspace bound (vr_set_smoothing_workspace: bytes of one of the two buffers; 0, the default: 2 GiB or what the
+   device has free), else z slabs of it, so device memory does not bound the volume size; the voxels are the same bits for
+   every slab size.  A bound below one slab's planes (2 r_z + 1) gives VR_E_NOMEM. */
+int vr_smooth_volume(vr_handle h, float sigma_x, float sigma_y, float sigma_z);
+int vr_get_smoothing(vr_handle h, float sigma3[3]);                /* (0, 0, 0): not smoothed */
+int vr_smooth_weights(float sigma, float *w, int capacity, int *radius);   /* host only, no handle */
+int vr_set_smoothing_workspace(vr_handle h, uint64_t bytes);
+/* measurement aid: HIP-event time, in ms, of the passes of the last vr_smooth_volume that ran any (first launch to last,
+   every slab; allocations, the range scan and host work excluded); 0 before the first and after a call that ran none */
+int vr_get_smoothing_ms(vr_handle h, float *ms);
 /* kernel selection: 0 = automatic (specialised kernels when the configuration allows; launches far from filling the
    chip -- fewer than 256 active 32x16 tiles, 1024 when the view is oblique to the volume axes -- use the 4-wavefront
    relay kernel; the fast kernel runs its software-pipelined batch loop unless alpha_scale >= 0.5),

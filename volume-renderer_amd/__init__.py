@@ -20,6 +20,7 @@ from .renderer import (  # noqa: F401
     load_library,
     read_pvm_volume,
     reslice_geometry,
+    smooth_weights,
     symbols_declared_in_header,
 )
 
@@ -35,5 +36,6 @@ __all__ = [
     "load_library",
     "read_pvm_volume",
     "reslice_geometry",
+    "smooth_weights",
     "symbols_declared_in_header",
 ]

@@ -18,6 +18,7 @@
 #include "vr_iso.h"
 #include "vr_reslice.h"
 #include "vr_shade.h"
+#include "vr_smooth.h"
 #include "vr_kernels.h"
 
 namespace vr {
@@ -172,6 +173,7 @@ bool RendererCore::loadShader(std::string fn, bool reload)
         check(launch_warm_iso(stream()), "module pre-load (isosurface)");
         check(launch_warm_reslice(stream()), "module pre-load (reslice)");
         check(launch_warm_shade(stream()), "module pre-load (shading)");
+        check(launch_warm_smooth(stream()), "module pre-load (smoothing)");
         check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
         tslab_warm_ = false;
         if (filter == 1) warmTrilinear();
@@ -219,7 +221,14 @@ size_t RendererCore::storageVoxels(int nx, int ny, int nz, int lay) const
 void RendererCore::freeVolume()
 {
     if (d_vol_) { (void)hipFree(d_vol_); d_vol_ = nullptr; vol_alloc_bytes_ = 0; }
+    if (d_loaded_) { (void)hipFree(d_loaded_); d_loaded_ = nullptr; loaded_alloc_bytes_ = 0; }
+    smooth_sigma_[0] = smooth_sigma_[1] = smooth_sigma_[2] = 0.0f;
     res_dims_[0] = res_dims_[1] = res_dims_[2] = 0; res_bytes_ = 0;
+    dropDerived();
+}
+
+void RendererCore::dropDerived()
+{
     if (d_skip_grid_) { (void)hipFree(d_skip_grid_); d_skip_grid_ = nullptr; skip_grid_cells_ = 0; }
     if (tile_table_skip_sig_ != 0) tile_table_skip_sig_ = -1;            // (an order built on the old volume's visibility)
     if (d_vol12_) { (void)hipFree(d_vol12_); d_vol12_ = nullptr; vol12_bytes_ = 0; }
@@ -230,16 +239,26 @@ void RendererCore::freeVolume()
     apron_perm_failed_ = false;
 }
 
+void *RendererCore::allocVolumeBuffer(int nx, int ny, int nz, int bytes, int lay, size_t &alloc_bytes)
+{
+    // + one x/y slab of slack so a one-past-the-edge index can never fault
+    const size_t need = (storageVoxels(nx, ny, nz, lay) + (size_t)nx * (size_t)ny + 256) * (size_t)bytes;
+    void *p = nullptr;
+    check(hipMalloc(&p, need), "hipMalloc(volume)");
+    alloc_bytes = need;
+    if (lay != 0) {
+        const hipError_t e = hipMemsetAsync(p, 0, need, stream());
+        if (e != hipSuccess) { (void)hipFree(p); check(e, "hipMemset(volume)"); }
+    }
+    return p;
+}
+
 void RendererCore::allocVolume(int nx, int ny, int nz, int bytes, int lay)
 {
     requireDevice("volume upload");
     freeVolume();
-    // + one x/y slab of slack so a one-past-the-edge index can never fault
-    const size_t need = (storageVoxels(nx, ny, nz, lay) + (size_t)nx * (size_t)ny + 256) * (size_t)bytes;
-    check(hipMalloc(&d_vol_, need), "hipMalloc(volume)");
-    vol_alloc_bytes_ = need;
+    d_vol_ = allocVolumeBuffer(nx, ny, nz, bytes, lay, vol_alloc_bytes_);
     vol_layout_ = lay;
-    if (lay != 0) check(hipMemsetAsync(d_vol_, 0, need, stream()), "hipMemset(volume)");
 }
 
 void RendererCore::setVolume(const void *host, int nx, int ny, int nz, int bytes, float sx, float sy, float sz)
@@ -324,18 +343,163 @@ void RendererCore::setLayout(int lay)
     if (!d_vol_ || vol_layout_ == lay) return;
     requireDevice("setLayout");
     const int nx = res_dims_[0], ny = res_dims_[1], nz = res_dims_[2], bytes = res_bytes_;
-    const int old_layout = vol_layout_;
-    const size_t old_alloc = vol_alloc_bytes_;
-    void *old = d_vol_;
-    d_vol_ = nullptr;
-    auto keep = [&]() { res_dims_[0] = nx; res_dims_[1] = ny; res_dims_[2] = nz; res_bytes_ = bytes; };   // allocVolume drops the resident state
-    try { allocVolume(nx, ny, nz, bytes, lay); } catch (...) { d_vol_ = old; vol_layout_ = old_layout; vol_alloc_bytes_ = old_alloc; keep(); throw; }
-    keep();
-    hipError_t e = launch_relayout(old, d_vol_, bytes, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz,
-                                   bricksX(nx), bricksY(ny), lay == 0 ? 1 : 0, stream());
-    if (e == hipSuccess) e = hipStreamSynchronize(stream());
-    (void)hipFree(old);
-    check(e, "relayout");
+    // the rendered volume and, beside a smoothed one, the loaded volume: both into new storage, then swapped in together
+    // (a failure leaves the handle as it was); the smoothing is not computed again
+    void *fresh[2] = {nullptr, nullptr}, *old[2] = {d_vol_, d_loaded_};
+    size_t fresh_bytes[2] = {0, 0};
+    hipError_t e = hipSuccess;
+    try {
+        for (int b = 0; b < 2 && e == hipSuccess; b++) {
+            if (!old[b]) continue;
+            fresh[b] = allocVolumeBuffer(nx, ny, nz, bytes, lay, fresh_bytes[b]);
+            e = launch_relayout(old[b], fresh[b], bytes, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, bricksX(nx), bricksY(ny), lay == 0 ? 1 : 0, stream());
+        }
+    } catch (...) {
+        (void)hipStreamSynchronize(stream());
+        for (void *q : fresh) if (q) (void)hipFree(q);
+        throw;
+    }
+    const hipError_t es = hipStreamSynchronize(stream());
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        for (void *q : fresh) if (q) (void)hipFree(q);
+        check(e, "relayout");
+    }
+    for (void *q : old) if (q) (void)hipFree(q);
+    d_vol_ = fresh[0]; vol_alloc_bytes_ = fresh_bytes[0];
+    d_loaded_ = fresh[1]; loaded_alloc_bytes_ = fresh_bytes[1];
+    vol_layout_ = lay;
+    dropDerived();
+}
+
+// ---------------------------------------------------------------- smoothing (vr_smooth_volume)
+// The passes of one smoothing, src -> dst (both allocVolume storage in vol_layout_): x, then y, then z, an axis with sigma 0
+// skipped.  With one pass the voxels go straight from src to dst.  With more, fp32 planes carry the intermediates: the whole
+// volume's where one buffer fits the workspace bound, else z slabs -- the passes before z then also cover the r_z planes on
+// either side of the slab, which the z pass reads (every plane of a slab is computed from the same inputs by the same
+// operations as in one piece: the result does not depend on the slab size).  The buffers are freed before this returns.
+void RendererCore::smoothPasses(const void *src, void *dst, const float sigma[3])
+{
+    const int nx = res_dims_[0], ny = res_dims_[1], nz = res_dims_[2];
+    float w[3][2 * kSmoothMaxRadius + 1];
+    int r[3] = {0, 0, 0}, axes[3], n = 0;
+    for (int a = 0; a < 3; a++)
+        if (sigma[a] > 0.0f) {
+            if (!smooth_weights(sigma[a], w[a], 2 * kSmoothMaxRadius + 1, &r[a])) throw std::invalid_argument("smoothVolume: bad sigma");
+            axes[n++] = a;
+        }
+    SmoothPass S = {};
+    S.bytes_per_voxel = res_bytes_; S.layout = vol_layout_;
+    S.nx = nx; S.ny = ny; S.nz = nz;
+    auto pass = [&](int a, const void *in, bool in_float, void *out, bool out_float, int buf_z0, int buf_planes, int z0, int z1) {
+        S.in = in; S.out = out; S.in_float = in_float; S.out_float = out_float;
+        S.in_z0 = S.out_z0 = buf_z0; S.in_planes = S.out_planes = buf_planes;
+        S.axis = a; S.z_begin = z0; S.z_end = z1; S.radius = r[a]; S.weights = w[a];
+        return launch_smooth_pass(S, stream());
+    };
+    // the passes between ev0_ and ev1_ (the events render() times frames with): lastSmoothMs
+    auto finish = [&](hipError_t e) {
+        if (e == hipSuccess) e = hipEventRecord(ev1_, stream());
+        const hipError_t es = hipStreamSynchronize(stream());
+        if (e == hipSuccess) e = es;
+        if (e == hipSuccess) e = hipEventElapsedTime(&last_smooth_ms_, ev0_, ev1_);
+        return e;
+    };
+    last_smooth_ms_ = 0.0f;
+    if (n == 1) {
+        hipError_t e = hipEventRecord(ev0_, stream());
+        if (e == hipSuccess) e = pass(axes[0], src, false, dst, false, 0, 0, 0, nz);
+        check(finish(e), "smooth kernel");
+        return;
+    }
+    const int rz = sigma[2] > 0.0f ? r[2] : 0;           // planes either side of a slab the passes before z must cover
+    const uint64_t plane_bytes = (uint64_t)nx * (uint64_t)ny * sizeof(float);
+    const int nbuf = n - 1;
+    uint64_t bound = smooth_workspace_limit;
+    if (bound == 0) {
+        bound = 2ull << 30;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            const uint64_t reserve = std::max<uint64_t>(kCopyReserveBytes, (uint64_t)total_b / 10);   // (what copyFits keeps free)
+            bound = std::min<uint64_t>(bound, (uint64_t)free_b > reserve ? ((uint64_t)free_b - reserve) / (uint64_t)nbuf : 0);
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    uint64_t planes = std::min<uint64_t>(bound / plane_bytes, (uint64_t)nz);
+    if (planes < (uint64_t)std::min(nz, 2 * rz + 1))
+        throw DeviceMemoryError(hipErrorOutOfMemory, "smoothVolume: the workspace cannot hold one slab of fp32 planes");
+    const int slab = planes >= (uint64_t)nz ? nz : (int)planes - 2 * rz;      // output planes per slab
+    void *buf[2] = {nullptr, nullptr};
+    for (int b = 0; b < nbuf; b++)
+        if (hipMalloc(&buf[b], planes * plane_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            if (buf[0]) (void)hipFree(buf[0]);
+            throw DeviceMemoryError(hipErrorOutOfMemory, "smoothVolume: hipMalloc(fp32 planes) failed");
+        }
+    hipError_t e = hipEventRecord(ev0_, stream());
+    for (int s0 = 0; s0 < nz && e == hipSuccess; s0 += slab) {
+        const int s1 = std::min(s0 + slab, nz), e0 = std::max(s0 - rz, 0), e1 = std::min(s1 + rz, nz);
+        const void *in = src;
+        for (int k = 0; k < n && e == hipSuccess; k++) {
+            const bool last = k == n - 1;
+            void *out = last ? dst : buf[k & 1];
+            e = pass(axes[k], in, k > 0, out, !last, e0, e1 - e0, last ? s0 : e0, last ? s1 : e1);
+            in = out;
+        }
+    }
+    e = finish(e);
+    for (void *q : buf) if (q) (void)hipFree(q);
+    check(e, "smooth kernel");
+}
+
+void RendererCore::smoothVolume(float sigma_x, float sigma_y, float sigma_z)
+{
+    const float sigma[3] = {sigma_x, sigma_y, sigma_z};
+    for (float s : sigma)
+        if (!std::isfinite(s) || s < 0.0f || s > kSmoothMaxSigma) throw std::invalid_argument("smoothVolume: every sigma must be finite and in [0, 8] voxels");
+    requireDevice("smoothVolume");
+    if (!d_vol_) throw std::runtime_error("smoothVolume: no dataset loaded");
+    check(hipStreamSynchronize(stream()), "hipStreamSynchronize");      // frames in flight read the buffers replaced below
+    const bool off = sigma_x == 0.0f && sigma_y == 0.0f && sigma_z == 0.0f;
+    if (off && !d_loaded_) return;                                       // rendering the loaded volume already
+    // The volume to render next: the loaded one again, or a new buffer the passes fill.  It is swapped in first and swapped back
+    // if the range scan fails, so a call that throws leaves the handle as it was.
+    void *next = d_loaded_;
+    size_t next_bytes = loaded_alloc_bytes_;
+    if (!off) {
+        try {
+            next = allocVolumeBuffer(res_dims_[0], res_dims_[1], res_dims_[2], res_bytes_, vol_layout_, next_bytes);
+        } catch (const HipError &err) {
+            (void)hipGetLastError();
+            throw DeviceMemoryError(err.code, std::string("smoothVolume: ") + err.what());
+        }
+        try { smoothPasses(d_loaded_ ? d_loaded_ : d_vol_, next, sigma); } catch (...) { (void)hipStreamSynchronize(stream()); (void)hipFree(next); throw; }
+    }
+    void *const old_vol = d_vol_;
+    const size_t old_bytes = vol_alloc_bytes_;
+    const int keep[8] = {min_val, max_val, min_dataset_val, max_dataset_val, exact_min_, exact_max_, 0, 0};
+    d_vol_ = next; vol_alloc_bytes_ = next_bytes;
+    try {
+        scanDatasetRange();                                              // the ranges of the rendered volume; it also sets the window from the data ...
+    } catch (...) {
+        (void)hipStreamSynchronize(stream());
+        d_vol_ = old_vol; vol_alloc_bytes_ = old_bytes;
+        min_val = keep[0]; max_val = keep[1]; min_dataset_val = keep[2]; max_dataset_val = keep[3]; exact_min_ = keep[4]; exact_max_ = keep[5];
+        if (!off) (void)hipFree(next);
+        throw;
+    }
+    min_val = keep[0]; max_val = keep[1];                                // ... which is the user's and stays; no message, camera and uniforms untouched
+    if (off) {
+        (void)hipFree(old_vol);                                          // the smoothed volume
+        d_loaded_ = nullptr; loaded_alloc_bytes_ = 0;
+    } else if (d_loaded_) {
+        (void)hipFree(old_vol);                                          // the earlier smoothing result
+    } else {
+        d_loaded_ = old_vol; loaded_alloc_bytes_ = old_bytes;
+    }
+    for (int a = 0; a < 3; a++) smooth_sigma_[a] = sigma[a];
+    dropDerived();                                                       // what a load leaves behind for new voxels
 }
 
 // min/max scan of src/RendererCore.cpp:360-384 as a device reduction
@@ -1243,7 +1407,7 @@ void RendererCore::residentBytes(uint64_t &volume, uint64_t &copies, uint64_t &o
     copies = copiesBytes();
     const uint64_t px = (uint64_t)framebuffer_size[0] * (uint64_t)framebuffer_size[1];
     other = (d_fb_ ? px * 16 : 0) + (d_tf_ ? 256 * 16 : 0) + (uint64_t)spp_capacity_ * 4 + (d_scratch_ ? 264 * 4 : 0) +
-            (d_skip_grid_ ? (uint64_t)skip_grid_cells_ * 2 : 0) + (uint64_t)rgba8_capacity_ + (uint64_t)present_capacity_ * kPresentSlots +
+            (d_skip_grid_ ? (uint64_t)skip_grid_cells_ * 2 : 0) + (uint64_t)loaded_alloc_bytes_ + (uint64_t)rgba8_capacity_ + (uint64_t)present_capacity_ * kPresentSlots +
             ((uint64_t)tile_table_capacity_ + (uint64_t)tile_table_tall_capacity_ + (uint64_t)tile_table_small_capacity_ + (uint64_t)tile_work_capacity_) * 4;
 }
 

@@ -22,6 +22,9 @@ struct HipError : std::runtime_error {
     hipError_t code;
     HipError(hipError_t c, const std::string &what) : std::runtime_error(what), code(c) {}
 };
+struct DeviceMemoryError : HipError {         // a device allocation a call cannot do without failed (VR_E_NOMEM)
+    using HipError::HipError;
+};
 struct NoDeviceError : std::runtime_error {
     using std::runtime_error::runtime_error;
 };
@@ -132,6 +135,15 @@ public:
     // 1, 2, 4, ..., 128: std::invalid_argument, the state unchanged
     void setShading(bool enable, float ambient, float diffuse, float specular, int shininess);
     void getShading(int *enable, float *ambient, float *diffuse, float *specular, int *shininess) const;
+    // Gaussian smoothing of the resident volume (vr_smooth_volume): always computed from the volume AS LOADED, which stays
+    // resident beside the smoothed one (d_loaded_); (0, 0, 0) drops the smoothed volume.  A sigma that is not finite or outside
+    // [0, 8]: std::invalid_argument; a device allocation that fails: DeviceMemoryError; either way nothing changes.
+    void smoothVolume(float sigma_x, float sigma_y, float sigma_z);
+    void getSmoothing(float sigma3[3]) const { for (int a = 0; a < 3; a++) sigma3[a] = smooth_sigma_[a]; }
+    float lastSmoothMs() const { return last_smooth_ms_; }   // HIP-event time of the last smoothVolume's passes (first launch to last; 0: none ran)
+    // upper bound on the bytes of ONE of smoothVolume's two fp32 plane buffers (vr_set_smoothing_workspace); 0: automatic -- the
+    // whole volume's planes where they fit in 2 GiB and in the free device memory, z slabs of the volume otherwise
+    uint64_t smooth_workspace_limit = 0;
 
     int filter = 0, accum = 0, skip_empty = 0;
     int layout = 1;          // VR_LAYOUT_BRICKED: the faster HBM layout is the default (vr_set_layout)
@@ -156,8 +168,12 @@ private:
     int device_ = -1;
     hipStream_t own_stream_ = nullptr, user_stream_ = nullptr;
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
-    void *d_vol_ = nullptr;
+    void *d_vol_ = nullptr;                  // the volume the kernels render: as loaded, or smoothed
     size_t vol_alloc_bytes_ = 0;
+    void *d_loaded_ = nullptr;               // while d_vol_ is a smoothed volume: the loaded one (same dimensions, type and layout)
+    size_t loaded_alloc_bytes_ = 0;
+    float smooth_sigma_[3] = {0.0f, 0.0f, 0.0f};
+    float last_smooth_ms_ = 0.0f;
     // geometry and voxel type of the volume that is RESIDENT (set only after a successful upload).
     // tex3D_dim / datasize_bytes above are GUI inputs of readVolumeData, like the reference's fields;
     // the reference's shader reads textureSize() of the uploaded texture (VolumeRenderer.cs:62), not them.
@@ -289,7 +305,10 @@ private:
     void requireDevice(const char *what) const;
     void check(hipError_t e, const char *what) const;
     void freeVolume();
+    void dropDerived();                      // everything built from the voxels of d_vol_: packed copy, apron copies, skip grid, the tile order under skipping
     void allocVolume(int nx, int ny, int nz, int bytes, int layout);
+    void *allocVolumeBuffer(int nx, int ny, int nz, int bytes, int layout, size_t &alloc_bytes);   // allocVolume's storage contract: zeroed brick padding, the slack slab
+    void smoothPasses(const void *src, void *dst, const float sigma[3]);
     size_t storageVoxels(int nx, int ny, int nz, int layout) const;
     void afterVolumeLoaded(const std::string &name);
     void scanDatasetRange();

@@ -11,6 +11,7 @@
 #include "renderer_core.h"
 #include "vr_handle.h"
 #include "volume_io.h"
+#include "vr_smooth.h"
 
 
 namespace {
@@ -32,6 +33,8 @@ int guarded(vr_handle h, F &&f)
         return VR_OK;
     } catch (const vr::NoDeviceError &e) {
         return fail(h, VR_E_NO_DEVICE, e.what());
+    } catch (const vr::DeviceMemoryError &e) {
+        return fail(h, VR_E_NOMEM, e.what());
     } catch (const vr::HipError &e) {
         return fail(h, VR_E_HIP, e.what());
     } catch (const vr::IoError &e) {
@@ -350,6 +353,37 @@ int vr_get_shading(vr_handle h, int *enable, float *ambient, float *diffuse, flo
 {
     if (!h) return VR_E_INVALID;
     h->core.getShading(enable, ambient, diffuse, specular, shininess);
+    return VR_OK;
+}
+
+int vr_smooth_volume(vr_handle h, float sigma_x, float sigma_y, float sigma_z)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.smoothVolume(sigma_x, sigma_y, sigma_z); });
+}
+
+int vr_get_smoothing(vr_handle h, float sigma3[3])
+{
+    if (!h || !sigma3) return VR_E_INVALID;
+    h->core.getSmoothing(sigma3);
+    return VR_OK;
+}
+
+int vr_get_smoothing_ms(vr_handle h, float *ms)
+{
+    if (!h || !ms) return VR_E_INVALID;
+    *ms = h->core.lastSmoothMs();
+    return VR_OK;
+}
+
+int vr_smooth_weights(float sigma, float *w, int capacity, int *radius)
+{
+    return vr::smooth_weights(sigma, w, capacity, radius) ? VR_OK : VR_E_INVALID;
+}
+
+int vr_set_smoothing_workspace(vr_handle h, uint64_t bytes)
+{
+    if (!h) return VR_E_INVALID;
+    h->core.smooth_workspace_limit = bytes;
     return VR_OK;
 }
 

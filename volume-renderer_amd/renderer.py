@@ -125,6 +125,11 @@ def load_library() -> C.CDLL:
         "vr_read_reslice_values": (i32, [h, C.POINTER(f32), C.c_size_t]),
         "vr_set_shading": (i32, [h, i32, f32, f32, f32, i32]),
         "vr_get_shading": (i32, [h, C.POINTER(i32), C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), C.POINTER(i32)]),
+        "vr_smooth_volume": (i32, [h, f32, f32, f32]),
+        "vr_get_smoothing": (i32, [h, C.POINTER(f32)]),
+        "vr_smooth_weights": (i32, [f32, C.POINTER(f32), i32, C.POINTER(i32)]),
+        "vr_set_smoothing_workspace": (i32, [h, C.c_uint64]),
+        "vr_get_smoothing_ms": (i32, [h, C.POINTER(f32)]),
         "vr_set_autotune": (i32, [h, i32]),
         "vr_export_choices": (i32, [h, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
         "vr_import_choices": (i32, [h, C.c_void_p, C.c_size_t, C.POINTER(i32)]),
@@ -212,6 +217,16 @@ def checksum(data: np.ndarray) -> int:
 
 def _fp(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def smooth_weights(sigma) -> np.ndarray:
+    """vr_smooth_weights: the 2r + 1 fp32 weights of one smoothing pass, r = ceil(3 sigma); sigma in (0, 8] voxels"""
+    w = np.zeros(49, dtype=np.float32)
+    r = C.c_int(0)
+    rc = load_library().vr_smooth_weights(float(sigma), _fp(w), w.size, C.byref(r))
+    if rc != VR_OK:
+        raise VRError(rc, f"smooth_weights: sigma {sigma!r} is outside (0, 8]")
+    return w[:2 * r.value + 1].copy()
 
 
 def reslice_geometry(dims, spacing, center_mm, normal, up, pixel_mm, slab_step_mm, fb_size) -> np.ndarray:
@@ -615,6 +630,32 @@ class RendererCore:
         a, d, s = C.c_float(0.0), C.c_float(0.0), C.c_float(0.0)
         self._check(self._lib.vr_get_shading(self._h, C.byref(e), C.byref(a), C.byref(d), C.byref(s), C.byref(n)))
         return dict(enable=bool(e.value), ambient=a.value, diffuse=d.value, specular=s.value, shininess=int(n.value))
+
+    def smoothVolume(self, sigma_voxels=None, sigma_mm=None):
+        """vr_smooth_volume: Gaussian smoothing of the volume as loaded.  Give exactly one of sigma_voxels (a number or one per
+        volume axis, x first) and sigma_mm (the same in the spacing's units: divided per axis by the spacing of dims)."""
+        if (sigma_voxels is None) == (sigma_mm is None):
+            raise ValueError("smoothVolume: give exactly one of sigma_voxels and sigma_mm")
+        s = np.broadcast_to(np.asarray(sigma_voxels if sigma_mm is None else sigma_mm, dtype=np.float64), (3,)).copy()
+        if sigma_mm is not None:
+            s = s / np.asarray(self.dims[1], dtype=np.float64)
+        self._check(self._lib.vr_smooth_volume(self._h, float(s[0]), float(s[1]), float(s[2])))
+
+    @property
+    def smoothing(self):
+        """the sigmas in voxels per volume axis of the volume being rendered; (0, 0, 0): the volume as loaded"""
+        s = np.zeros(3, dtype=np.float32)
+        self._check(self._lib.vr_get_smoothing(self._h, _fp(s)))
+        return tuple(float(v) for v in s)
+
+    def smoothingMs(self) -> float:
+        """HIP-event time of the last smoothVolume's passes, ms"""
+        ms = C.c_float(0.0)
+        self._check(self._lib.vr_get_smoothing_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def setSmoothingWorkspace(self, nbytes):
+        self._check(self._lib.vr_set_smoothing_workspace(self._h, C.c_uint64(int(nbytes))))
 
     def setKernelVariant(self, variant):
         self._check(self._lib.vr_set_kernel_variant(self._h, variant))
