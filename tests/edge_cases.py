@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE ONLY -- the volume sampler's edges, for tests/test_mode_edges_{cpu,gpu}.py.
 
-The isosurface, reslice and shading kernels each carry their own copy of the sampler (address terms, x-pair loads, edge clamps,
-trilinear lerps).  This is the shared recipe that takes every copy to where a sampler goes wrong: volumes with an axis of 1 to 8
+The isosurface, reslice and shading kernels share one sampler (csrc/vr_sampler.h: address terms, x-pair loads, edge clamps,
+trilinear lerps).  This is the shared recipe that takes every kernel to where a sampler goes wrong: volumes with an axis of 1 to 8
 voxels, the first and the last voxel of the buffer, cameras inside / grazing / far from the box, images smaller than a tile.
 
 Volume kinds.  `corners`: a background below vmax // 3 with the first and the last voxel of the buffer at vmax (255 / 4095), so a

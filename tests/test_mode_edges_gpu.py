@@ -2,11 +2,12 @@
 voxel of the buffer, cameras inside / grazing / far, images smaller than a tile, zero gradients, max == min, the +1000 quirk, the
 truncated grid, the 10 000-step budget, the tail of the reslice loop and iso values that meet a stored value exactly.
 
-Each of vr_iso.hip, vr_reslice.hip and vr_shade.hip carries its own copy of the sampler; the composite copy's edge tests (the tiny
-volumes of test_parity_gpu.py) do not reach them.  Every comparison is against the mode's CPU definition (tests/iso_ref,
-tests/reslice_ref, tests/shade_ref; tests/test_mode_edges_cpu.py anchors those at the same edges) on every output the mode has --
-RGBA bits, per-pixel counts, depth bits, reslice value bits.  Windows and iso values are in STORED units and the handles run with
-setQuirks(0), unless a case says that it converts through the +1000 of VR_QUIRK_U16_OFFSET.
+vr_iso.hip, vr_reslice.hip and vr_shade.hip share one sampler (csrc/vr_sampler.h) but each wraps its own march, gradient and
+reduction around it; the composite kernels' edge tests (the tiny volumes of test_parity_gpu.py) do not reach them.  Every
+comparison is against the mode's CPU definition (tests/iso_ref, tests/reslice_ref, tests/shade_ref; tests/test_mode_edges_cpu.py
+anchors those at the same edges) on every output the mode has -- RGBA bits, per-pixel counts, depth bits, reslice value bits.
+Windows and iso values are in STORED units and the handles run with setQuirks(0), unless a case says that it converts through
+the +1000 of VR_QUIRK_U16_OFFSET.
 """
 import importlib.util
 from pathlib import Path
@@ -110,8 +111,8 @@ def params(oracle, size, cam, spacing, view, filt, **kw):
 def test_thin_volumes_read_the_first_and_last_voxel(vra, oracle, refs, handle, mode, filt, dtype):
     """the seeded frames of edge_cases.thin_cases on `corners` volumes of the whole pool; test_mode_edges_cpu.py shows that more
     than half of them change with the last voxel of the buffer and more than half with the first.  (The x-pair load of the last
-    voxel reaches past the buffer, and a partly out-of-range buffer load returns 0 for all of it: the composite copy's
-    test_trilinear_on_tiny_volumes_reads_the_last_voxel, for the three other copies.)  One voxel type per test, to keep each
+    voxel reaches past the buffer, and a partly out-of-range buffer load returns 0 for all of it: the composite kernels'
+    test_trilinear_on_tiny_volumes_reads_the_last_voxel, for the three other kernels.)  One voxel type per test, to keep each
     one shorter than the existing random matrices."""
     r = handle
     frames = shown = 0

@@ -1,6 +1,7 @@
-// vr_device.h -- device-side helpers shared by the ray-march translation units
-// (vr_kernels.hip, vr_tslab.hip): GLSL built-ins restated, ray set-up, the slab test, voxel
-// addressing, the safe-prefix bound.  See vr_kernels.hip for the arithmetic contract.
+// vr_device.h -- device-side helpers shared by the ray-march translation units (vr_kernels.hip,
+// vr_tslab.hip, vr_iso.hip, vr_reslice.hip, vr_shade.hip): GLSL built-ins restated, ray set-up, the
+// slab test, voxel addressing, the safe-prefix bound.  The volume sampler of the one-pixel-per-lane
+// kernels is vr_sampler.h.  See vr_kernels.hip for the arithmetic contract.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -19,6 +19,9 @@ bool tri_slab_candidate(const FrameParams &P, const LaunchConfig &L);
 
 // local image rows one launch covers (stripe padding included)
 int launch_local_rows(const FrameParams &P);
+// blocks of a launch whose 16x16-pixel tiles tile_of_block() deals out: every XCD gets ceil(tiles_y / 8) tile rows' worth of
+// slots; extras are padding
+static inline unsigned padded_blocks(unsigned tiles_x, unsigned tiles_y) { return ((tiles_y + 7u) / 8u) * tiles_x * 8u; }
 
 // The ray-march launch (replaces glDispatchCompute, src/RendererCore.cpp:150).
 // spp != nullptr selects the instrumented variant that also stores fetch counts.

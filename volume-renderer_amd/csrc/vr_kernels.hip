@@ -25,6 +25,7 @@
 
 #include "vr_device.h"
 #include "vr_lds_dma.h"
+#include "vr_sampler.h"
 
 // Translation units: the ray-march kernels of one (voxel type, layout) pair are ~150 template
 // instances each, so the Makefile compiles this file five times in parallel:
@@ -62,13 +63,6 @@ __global__ void certify_div_kernel(float b, float r, unsigned *bad)
 #include "vr_relay.hip"
 
 // ------------------------------------------------------------------ launchers
-
-[[maybe_unused]] static inline unsigned padded_blocks(unsigned tiles_x, unsigned tiles_y)
-{
-    // every XCD gets ceil(tiles_y/8) tile rows' worth of slots; extras are padding
-    const unsigned rows0 = (tiles_y + 7u) / 8u;
-    return rows0 * tiles_x * 8u;
-}
 
 template <typename VoxelT, int LAYOUT, bool COUNT>
 static hipError_t launch_generic(const FrameParams &P, const LaunchConfig &L, const void *vol, const float4 *tf,

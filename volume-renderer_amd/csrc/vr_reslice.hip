@@ -17,7 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "vr_device.h"
+#include "vr_sampler.h"
 #include "vr_reslice.h"
 
 #ifndef VR_RESLICE_TU
@@ -35,75 +35,11 @@ __global__ __launch_bounds__(256) void reslice_kernel(const FrameParams P, const
     unsigned tx, ty;
     tile_of_block(blockIdx.x, tiles_x, tiles_y, tx, ty);
     if (tx == 0xffffffffu) return;
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const int lx = (int)(tx * 16u + (wave & 1u) * 8u + (lane & 7u));
-    const int ly = (int)(ty * 16u + (wave >> 1) * 8u + (lane >> 3));
-    int px = lx, py;
-    if (P.stripe_count > 1) {
-        const int s = ly / P.stripe_rows, r = ly % P.stripe_rows;
-        py = (s * P.stripe_count + P.stripe_index) * P.stripe_rows + r;
-    } else {
-        py = P.row_begin + ly;
-    }
-    if (px >= P.col_lim || py >= P.row_lim || py >= P.row_end) return;
+    int lx, ly, px, py;
+    if (!tile_pixel(P, tx, ty, lx, ly, px, py)) return;
 
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)vol, 0, BIG ? 0 : (int)pair_load_extent(vol_bytes), 0x00020000);
-    // per-axis terms of VoxelAddr<LAYOUT, false>::at(i, j, k) = X(i) + Y(j) + Z(k)  (mod 2^32), as in the generic kernel
-    auto term_x = [&](int i) -> uint32_t {
-        return LAYOUT == 0 ? (uint32_t)i : mad_u24((uint32_t)i >> BRICK_LX, 64u - (uint32_t)BRICK_X, (uint32_t)i);
-    };
-    auto term_y = [&](int j) -> uint32_t {
-        if (LAYOUT == 0) return mad_u24((uint32_t)j, (uint32_t)P.nx, 0u);
-        return mad_u24(BRICK_LY ? (uint32_t)j >> BRICK_LY : (uint32_t)j, P.bstride_y, BRICK_LY ? (uint32_t)j << BRICK_LX : 0u);
-    };
-    auto term_z = [&](int k) -> uint32_t {
-        if (LAYOUT == 0) return mad_u24(mad_u24((uint32_t)k, (uint32_t)P.ny, 0u), (uint32_t)P.nx, 0u);
-        return mad_u24(BRICK_LZ ? (uint32_t)k >> BRICK_LZ : (uint32_t)k, P.bstride_z, BRICK_LZ ? (uint32_t)k << (BRICK_LX + BRICK_LY) : 0u);
-    };
-    auto tap = [&](uint32_t off) -> float { return (float)VoxelFetch<VoxelT, false>::load(vol, rs, off); };
-    // NEAREST: voxel (i, j, k), inside the volume
-    auto voxel = [&](int i, int j, int k) -> float {
-        return BIG ? fetch_voxel<VoxelT, LAYOUT>(P, vol, i, j, k) : tap(term_x(i) + term_y(j) + term_z(k));
-    };
-    // TRILINEAR at continuous voxel coordinates (u, v, w): GL's linear rule, taps clamped to the edge, x then y then z, each lerp
-    // one fma -- the isosurface kernel's sampler.  32-bit offsets fetch each x pair with one load (the generic kernel's pair loads)
-    auto trilinear = [&](float u, float v, float w) -> float {
-        const float fu = floorf(u), fv = floorf(v), fw = floorf(w);
-        const float ax = u - fu, ay = v - fv, az = w - fw;
-        const int iu = (int)fu, iv = (int)fv, iw = (int)fw;
-        const int i0 = clampi(iu, 0, P.nx - 1), i1 = clampi(iu + 1, 0, P.nx - 1);
-        const int j0 = clampi(iv, 0, P.ny - 1), j1 = clampi(iv + 1, 0, P.ny - 1);
-        const int k0 = clampi(iw, 0, P.nz - 1), k1 = clampi(iw + 1, 0, P.nz - 1);
-        float c000, c100, c010, c110, c001, c101, c011, c111;
-        if (BIG) {
-            c000 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i0, j0, k0); c100 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i1, j0, k0);
-            c010 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i0, j1, k0); c110 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i1, j1, k0);
-            c001 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i0, j0, k1); c101 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i1, j0, k1);
-            c011 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i0, j1, k1); c111 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i1, j1, k1);
-        } else {
-            const uint32_t x0 = term_x(i0), x1 = term_x(i1), y0 = term_y(j0), y1 = term_y(j1);
-            const uint32_t z0 = term_z(k0), z1 = term_z(k1);
-            const bool pair = i1 == i0 + 1 && (LAYOUT == 0 || ((uint32_t)i0 & (BRICK_X - 1u)) != BRICK_X - 1u);
-            auto tap2 = [&](uint32_t off, float &lo, float &hi) {
-                if (sizeof(VoxelT) == 1) {
-                    const uint32_t q = (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rs, (int)off, 0, 0);
-                    lo = (float)(q & 0xffu); hi = (float)(q >> 8);
-                } else {
-                    const uint32_t q = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)(off << 1), 0, 0);
-                    lo = (float)(q & 0xffffu); hi = (float)(q >> 16);
-                }
-            };
-            tap2(x0 + y0 + z0, c000, c100); tap2(x0 + y1 + z0, c010, c110);
-            tap2(x0 + y0 + z1, c001, c101); tap2(x0 + y1 + z1, c011, c111);
-            if (!pair) {
-                c100 = tap(x1 + y0 + z0); c110 = tap(x1 + y1 + z0); c101 = tap(x1 + y0 + z1); c111 = tap(x1 + y1 + z1);
-            }
-        }
-        const float c00 = tri_lerp(c000, c100, ax), c10 = tri_lerp(c010, c110, ax);
-        const float c01 = tri_lerp(c001, c101, ax), c11 = tri_lerp(c011, c111, ax);
-        const float e0 = tri_lerp(c00, c10, ay), e1 = tri_lerp(c01, c11, ay);
-        return tri_lerp(e0, e1, az);
-    };
+    // NEAREST at a voxel inside the volume; TRILINEAR at continuous voxel coordinates (u, v, w)
+    const VolumeSampler<VoxelT, LAYOUT, BIG> S(P, vol, vol_bytes);
 
     // ---- the line: p = (o + X * du) + Y * dv per component, q_k = p + c_k * dw, c_k = (2k - (n - 1)) / 2 (exact)
     const float X = (float)px, Y = (float)py;
@@ -133,8 +69,8 @@ __global__ __launch_bounds__(256) void reslice_kernel(const FrameParams P, const
         float s[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            if (FILTER == 0) s[j] = voxel((int)qx[j], (int)qy[j], (int)qz[j]);        // r in [0, dim): truncation is the floor
-            else s[j] = trilinear(qx[j], qy[j], qz[j]);
+            if (FILTER == 0) s[j] = S.voxel((int)qx[j], (int)qy[j], (int)qz[j]);        // r in [0, dim): truncation is the floor
+            else s[j] = S.trilinear(qx[j], qy[j], qz[j]);
         }
         // ---- the reduction, in increasing k
 #pragma unroll
@@ -153,12 +89,10 @@ __global__ __launch_bounds__(256) void reslice_kernel(const FrameParams P, const
         const float value = MODE == 2 ? acc / (float)cnt : m;
         out = hu_offset ? value - 1000.0f : value;
         // window (the composite mode's rule; max == min: 0)
-        float v = gl_min(gl_max(value, P.fmin), P.fmax);
-        if (P.fden == 0.0f) v = 0.0f;
-        else if (v <= P.fmax && v >= P.fmin) v = divmode == DIV_CERT ? div_cert(v - P.fmin, P.fden, P.rden) : (v - P.fmin) / P.fden;
+        const float v = window_map(P, value, divmode);
         c0 = v; c1 = v; c2 = v; c3 = 1.0f;
         if (P.tf_len > 1) {
-            const int idx = clampi(floor_to_int_sat(v * (float)(P.tf_len - 1) + 0.5f), 0, P.tf_len - 1);
+            const int idx = tf_index(P, v);
             const float4 t = tf[idx];
             c0 = t.x; c1 = t.y; c2 = t.z;
         }
@@ -169,18 +103,12 @@ __global__ __launch_bounds__(256) void reslice_kernel(const FrameParams P, const
     if (spp) spp[pix] = cnt;
 }
 
-static inline unsigned reslice_padded_blocks(unsigned tiles_x, unsigned tiles_y)
-{
-    // as vr_kernels.hip: every XCD gets ceil(tiles_y / 8) tile rows' worth of slots; extras are padding
-    return ((tiles_y + 7u) / 8u) * tiles_x * 8u;
-}
-
 template <typename VoxelT, int LAYOUT, int FILTER, int MODE>
 static hipError_t launch_rs(const FrameParams &P, const LaunchConfig &L, const ResliceArgs &A, const void *vol, const float4 *tf,
                             float4 *fb, uint32_t *spp, unsigned tiles_x, unsigned tiles_y, hipStream_t st)
 {
     const int div = L.divmode_win == DIV_CERT ? DIV_CERT : DIV_EXACT;
-    const dim3 grid(reslice_padded_blocks(tiles_x, tiles_y)), block(256);
+    const dim3 grid(padded_blocks(tiles_x, tiles_y)), block(256);
     if (L.big_offsets)
         hipLaunchKernelGGL((reslice_kernel<VoxelT, LAYOUT, FILTER, MODE, true>), grid, block, 0, st, P, A.g, A.n, div, A.hu_offset, 0u,
                            (const VoxelT *)vol, tf, fb, spp, A.values, tiles_x, tiles_y);

@@ -21,7 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "vr_device.h"
+#include "vr_sampler.h"
 #include "vr_shade.h"
 
 #ifndef VR_SHADE_TU
@@ -46,80 +46,15 @@ __global__ __launch_bounds__(256) void raymarch_shade_kernel(const FrameParams P
     const bool use_tf = P.tf_len > 1;              // (the launcher refuses tf_len > 256)
     if (use_tf && (int)threadIdx.x < P.tf_len) s_tf[threadIdx.x] = tf[threadIdx.x];
     __syncthreads();
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const int lx = (int)(tx * 16u + (wave & 1u) * 8u + (lane & 7u));
-    const int ly = (int)(ty * 16u + (wave >> 1) * 8u + (lane >> 3));
-    int px = lx, py;
-    if (P.stripe_count > 1) {
-        const int s = ly / P.stripe_rows, r = ly % P.stripe_rows;
-        py = (s * P.stripe_count + P.stripe_index) * P.stripe_rows + r;
-    } else {
-        py = P.row_begin + ly;
-    }
-    if (px >= P.col_lim || py >= P.row_lim || py >= P.row_end) return;
+    int lx, ly, px, py;
+    if (!tile_pixel(P, tx, ty, lx, ly, px, py)) return;
 
     const Ray ray = compute_ray(P, (float)px + 0.5f, (float)py + 0.5f);
     float t_min = 0.0f, t_max = 0.0f;
     float d0 = 0.0f, d1 = 0.0f, d2 = 0.0f, d3 = 0.0f;
     uint32_t fetches = 0;
     if (intersect_ray_aabb(P, ray, t_min, t_max)) {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)vol, 0, BIG ? 0 : (int)pair_load_extent(vol_bytes), 0x00020000);
-        // per-axis terms of VoxelAddr<LAYOUT, false>::at(i, j, k) = X(i) + Y(j) + Z(k)  (mod 2^32), as in the generic kernel
-        auto term_x = [&](int i) -> uint32_t {
-            return LAYOUT == 0 ? (uint32_t)i : mad_u24((uint32_t)i >> BRICK_LX, 64u - (uint32_t)BRICK_X, (uint32_t)i);
-        };
-        auto term_y = [&](int j) -> uint32_t {
-            if (LAYOUT == 0) return mad_u24((uint32_t)j, (uint32_t)P.nx, 0u);
-            return mad_u24(BRICK_LY ? (uint32_t)j >> BRICK_LY : (uint32_t)j, P.bstride_y, BRICK_LY ? (uint32_t)j << BRICK_LX : 0u);
-        };
-        auto term_z = [&](int k) -> uint32_t {
-            if (LAYOUT == 0) return mad_u24(mad_u24((uint32_t)k, (uint32_t)P.ny, 0u), (uint32_t)P.nx, 0u);
-            return mad_u24(BRICK_LZ ? (uint32_t)k >> BRICK_LZ : (uint32_t)k, P.bstride_z, BRICK_LZ ? (uint32_t)k << (BRICK_LX + BRICK_LY) : 0u);
-        };
-        auto tap = [&](uint32_t off) -> float { return (float)VoxelFetch<VoxelT, false>::load(vol, rs, off); };
-        // NEAREST: voxel (i, j, k), indices already clamped
-        auto voxel = [&](int i, int j, int k) -> float {
-            return BIG ? fetch_voxel<VoxelT, LAYOUT>(P, vol, i, j, k) : tap(term_x(i) + term_y(j) + term_z(k));
-        };
-        // TRILINEAR at the sampler's own continuous coordinates (u, v, w) = tc * dim - 0.5: GL's linear rule, taps clamped to
-        // the edge, x then y then z, each lerp one fma.  32-bit offsets fetch each x pair with one load (the generic kernel's pair loads)
-        auto trilinear = [&](float u, float v, float w) -> float {
-            const float fu = floorf(u), fv = floorf(v), fw = floorf(w);
-            const float ax = u - fu, ay = v - fv, az = w - fw;
-            const int iu = (int)fu, iv = (int)fv, iw = (int)fw;
-            const int i0 = clampi(iu, 0, P.nx - 1), i1 = clampi(iu + 1, 0, P.nx - 1);
-            const int j0 = clampi(iv, 0, P.ny - 1), j1 = clampi(iv + 1, 0, P.ny - 1);
-            const int k0 = clampi(iw, 0, P.nz - 1), k1 = clampi(iw + 1, 0, P.nz - 1);
-            float c000, c100, c010, c110, c001, c101, c011, c111;
-            if (BIG) {
-                c000 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i0, j0, k0); c100 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i1, j0, k0);
-                c010 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i0, j1, k0); c110 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i1, j1, k0);
-                c001 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i0, j0, k1); c101 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i1, j0, k1);
-                c011 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i0, j1, k1); c111 = fetch_voxel<VoxelT, LAYOUT>(P, vol, i1, j1, k1);
-            } else {
-                const uint32_t x0 = term_x(i0), x1 = term_x(i1), y0 = term_y(j0), y1 = term_y(j1);
-                const uint32_t z0 = term_z(k0), z1 = term_z(k1);
-                const bool pair = i1 == i0 + 1 && (LAYOUT == 0 || ((uint32_t)i0 & (BRICK_X - 1u)) != BRICK_X - 1u);
-                auto tap2 = [&](uint32_t off, float &lo, float &hi) {
-                    if (sizeof(VoxelT) == 1) {
-                        const uint32_t q = (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rs, (int)off, 0, 0);
-                        lo = (float)(q & 0xffu); hi = (float)(q >> 8);
-                    } else {
-                        const uint32_t q = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)(off << 1), 0, 0);
-                        lo = (float)(q & 0xffffu); hi = (float)(q >> 16);
-                    }
-                };
-                tap2(x0 + y0 + z0, c000, c100); tap2(x0 + y1 + z0, c010, c110);
-                tap2(x0 + y0 + z1, c001, c101); tap2(x0 + y1 + z1, c011, c111);
-                if (!pair) {
-                    c100 = tap(x1 + y0 + z0); c110 = tap(x1 + y1 + z0); c101 = tap(x1 + y0 + z1); c111 = tap(x1 + y1 + z1);
-                }
-            }
-            const float c00 = tri_lerp(c000, c100, ax), c10 = tri_lerp(c010, c110, ax);
-            const float c01 = tri_lerp(c001, c101, ax), c11 = tri_lerp(c011, c111, ax);
-            const float e0 = tri_lerp(c00, c10, ay), e1 = tri_lerp(c01, c11, ay);
-            return tri_lerp(e0, e1, az);
-        };
+        const VolumeSampler<VoxelT, LAYOUT, BIG> S(P, vol, vol_bytes);
         auto nearest_index = [&](float tc, float fdim, int n) -> int { return clampi(floor_to_int_sat(tc * fdim), 0, n - 1); };
 
         const float EPSILON = 0.000001f;
@@ -175,14 +110,12 @@ __global__ __launch_bounds__(256) void raymarch_shade_kernel(const FrameParams P
                 visible = !cell_empty;
             }
             if (visible) {
-                float s = FILTER == 0 ? voxel(vi, vj, vk) : trilinear(u, v, w);
+                float s = FILTER == 0 ? S.voxel(vi, vj, vk) : S.trilinear(u, v, w);
                 // window (VolumeRenderer.cs:122-124; Q4: max == min defined as 0), the division certified like the composite kernels'
-                s = gl_min(gl_max(s, P.fmin), P.fmax);
-                if (P.fden == 0.0f) s = 0.0f;
-                else if (s <= P.fmax && s >= P.fmin) s = divmode_win == DIV_CERT ? div_cert(s - P.fmin, P.fden, P.rden) : (s - P.fmin) / P.fden;
+                s = window_map(P, s, divmode_win);
                 float c0 = s, c1 = s, c2 = s, a = s;
                 if (use_tf) {
-                    const int idx = clampi(floor_to_int_sat(s * (float)(P.tf_len - 1) + 0.5f), 0, P.tf_len - 1);
+                    const int idx = tf_index(P, s);
                     const float4 t = s_tf[idx];
                     c0 = t.x; c1 = t.y; c2 = t.z; a = t.w;
                 }
@@ -191,13 +124,13 @@ __global__ __launch_bounds__(256) void raymarch_shade_kernel(const FrameParams P
                     // ---- gradient: central differences of the same sampler at the sample, +-1 voxel per volume axis, clamped
                     float gx, gy, gz;
                     if (FILTER == 0) {
-                        gx = voxel(clampi(vi + 1, 0, P.nx - 1), vj, vk) - voxel(clampi(vi - 1, 0, P.nx - 1), vj, vk);
-                        gy = voxel(vi, clampi(vj + 1, 0, P.ny - 1), vk) - voxel(vi, clampi(vj - 1, 0, P.ny - 1), vk);
-                        gz = voxel(vi, vj, clampi(vk + 1, 0, P.nz - 1)) - voxel(vi, vj, clampi(vk - 1, 0, P.nz - 1));
+                        gx = S.voxel(clampi(vi + 1, 0, P.nx - 1), vj, vk) - S.voxel(clampi(vi - 1, 0, P.nx - 1), vj, vk);
+                        gy = S.voxel(vi, clampi(vj + 1, 0, P.ny - 1), vk) - S.voxel(vi, clampi(vj - 1, 0, P.ny - 1), vk);
+                        gz = S.voxel(vi, vj, clampi(vk + 1, 0, P.nz - 1)) - S.voxel(vi, vj, clampi(vk - 1, 0, P.nz - 1));
                     } else {
-                        gx = trilinear(u + 1.0f, v, w) - trilinear(u - 1.0f, v, w);
-                        gy = trilinear(u, v + 1.0f, w) - trilinear(u, v - 1.0f, w);
-                        gz = trilinear(u, v, w + 1.0f) - trilinear(u, v, w - 1.0f);
+                        gx = S.trilinear(u + 1.0f, v, w) - S.trilinear(u - 1.0f, v, w);
+                        gy = S.trilinear(u, v + 1.0f, w) - S.trilinear(u, v - 1.0f, w);
+                        gz = S.trilinear(u, v, w + 1.0f) - S.trilinear(u, v, w - 1.0f);
                     }
                     // volume axes -> box axes: the view's permutation, the z flip, dim / ext per axis
                     const float Gx = gx * gsx;
@@ -238,19 +171,13 @@ __global__ __launch_bounds__(256) void raymarch_shade_kernel(const FrameParams P
     if (spp) spp[pix] = fetches;
 }
 
-static inline unsigned shade_padded_blocks(unsigned tiles_x, unsigned tiles_y)
-{
-    // as vr_kernels.hip: every XCD gets ceil(tiles_y / 8) tile rows' worth of slots; extras are padding
-    return ((tiles_y + 7u) / 8u) * tiles_x * 8u;
-}
-
 template <typename VoxelT, int LAYOUT, int FILTER, bool SKIP>
 static hipError_t launch_shade(const FrameParams &P, const LaunchConfig &L, const ShadeArgs &A, const void *vol, const float4 *tf,
                                float4 *fb, uint32_t *spp, unsigned tiles_x, unsigned tiles_y, hipStream_t st)
 {
     const int div = L.divmode_tc == DIV_EXACT ? DIV_EXACT : DIV_CERT;
     const int div_win = L.divmode_win == DIV_CERT ? DIV_CERT : DIV_EXACT;
-    const dim3 grid(shade_padded_blocks(tiles_x, tiles_y)), block(256);
+    const dim3 grid(padded_blocks(tiles_x, tiles_y)), block(256);
     if (L.big_offsets)
         hipLaunchKernelGGL((raymarch_shade_kernel<VoxelT, LAYOUT, FILTER, SKIP, true>), grid, block, 0, st, P, div, div_win, 0u,
                            (const VoxelT *)vol, tf, fb, spp, A.skip_grid, A.skip_thresh, A.ambient, A.diffuse, A.specular,
