@@ -1,4 +1,4 @@
-"""The measured work model (RendererCore::tuneChoose, vr_set_autotune): what it settles on must be what a sweep of the forced
+"""The measured work model (vr::LaunchTuner behind RendererCore::tuneChoose, vr_set_autotune): what it settles on must be what a sweep of the forced
 kernel variants finds at sustained clocks -- also when it starts on a cold GPU (round-3 verdict: "can settle on a cold-clock
 measurement and never looks again") -- and a slider drag must not keep it exploring (round-3 advisor)."""
 import time
@@ -69,6 +69,36 @@ def test_a_slider_drag_does_not_keep_the_model_exploring(vra):
         off = sum(1 for c in seen[40:] if c != final)
         assert off <= 16, (final, off, seen[:60])                # one exploration per bucket crossed at most, not one per frame
         assert len(set(seen[-60:])) == 1
+
+
+def test_bursts_of_asynchronous_frames_explore_and_settle(vra):
+    """The asynchronous path -- renderAsync in bursts of 8, the ring of event pairs polled by the next launch -- explores through
+    LaunchTuner too: some early frame is a trial (bit 8), the last 60 of 400 are one settled choice (the one re-validation after
+    96 frames is long over), and the last frame is the bits a blocking render() of a second handle gives.  128^3 u16 noise
+    ball, 512 x 512, shard 3 of 8 in stripes of 16 rows (relay against fast kernel: a real choice)."""
+    R = vra.renderer
+
+    def fresh():
+        r = vra.RendererCore(0)
+        r.setup((512, 512)); assert r.loadShader("VolumeRenderer.cs"); r.setQuirks(0)
+        r.generateSynthetic(R.SYNTH_NOISE_BALL, (128, 128, 128), 2, 0x9E3779B9); r.setWindow(0, 4095); r.setAlpha(0.004)
+        r.setFilter(R.FILTER_NEAREST)
+        r.setRowStripes(16, 3, 8)
+        return r
+
+    with fresh() as a:
+        seen = []
+        while len(seen) < 400:
+            for _ in range(8):
+                a.renderAsync()
+                seen.append(a.last_launch_choice)
+            a.synchronize()
+        assert any(c & 256 for c in seen[:100]), seen[:100]      # it did explore (or the rest would pass vacuously)
+        assert all(c & 256 == 0 for c in seen[-60:]) and len(set(seen[-60:])) == 1, seen[-60:]
+        got = a.readPixels().copy()
+    with fresh() as b:
+        b.render()
+        assert np.array_equal(b.readPixels().view(np.uint32), got.view(np.uint32))
 
 
 def test_imported_choices_start_a_cold_handle_on_the_settled_kernel(vra):

@@ -6,7 +6,7 @@ evidence pass has measured a new blob (tools/round_evidence.sh, phase 0), turn i
 
     python tools/choices_text.py encode [profiles/launch_choices.bin] [profiles/launch_choices.json]
 
-Layout (renderer_core.cpp: ChoiceHeader / ChoiceRecord, little-endian): header "VRCHOICE", u32 version, u32 count, u64 build id,
+Layout (launch_tuner.h: ChoiceHeader / ChoiceRecord, little-endian): header "VRCHOICE", u32 version, u32 count, u64 build id,
 char[64] device model; then per entry u64 key, i32 ncand, i32 settled candidate, i32 heuristic candidate, i32 cand[8], 4 bytes padding.
 """
 from __future__ import annotations

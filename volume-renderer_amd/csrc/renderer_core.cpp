@@ -860,6 +860,26 @@ void RendererCore::refuseIsoGreyAlpha() const
         throw std::invalid_argument("render: the (grey, alpha) target format needs a grey mode (the isosurface mode is not one)");
 }
 
+// the skip grid's cells (8x8x8 voxels) per axis of the resident volume
+void RendererCore::setSkipCells(FrameParams &P) const
+{
+    P.cnx = (int32_t)((res_dims_[0] + 7) / 8); P.cny = (int32_t)((res_dims_[1] + 7) / 8); P.cnz = (int32_t)((res_dims_[2] + 7) / 8);
+}
+
+// a per-pixel float target beside the colour one (depth, values): grown to this frame's rows x width; a new allocation is filled
+// with the bit pattern `fill` (pixels no later frame writes read as "nothing here")
+void RendererCore::growFloatTarget(float *&d, size_t &capacity, int fill, const char *name)
+{
+    const int rows = std::max(localRows(), framebuffer_size[1]);
+    const size_t n = (size_t)rows * (size_t)framebuffer_size[0];
+    if (capacity >= n) return;
+    const std::string of = std::string("(") + name + ")";
+    if (d) { check(hipFree(d), ("hipFree" + of).c_str()); d = nullptr; capacity = 0; }
+    check(hipMalloc(reinterpret_cast<void **>(&d), std::max<size_t>(n, 1) * sizeof(float)), ("hipMalloc" + of).c_str());
+    capacity = n;
+    check(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d), fill, n, stream()), ("hipMemset" + of).c_str());
+}
+
 float4 *RendererCore::prepareLaunch(FrameParams &P, LaunchConfig &L)
 {
     refuseIsoGreyAlpha();
@@ -878,21 +898,13 @@ float4 *RendererCore::prepareLaunch(FrameParams &P, LaunchConfig &L)
         P.skip_empty = 0;
         iso_skip_grid_ = nullptr;
         if (skip_empty && ensureSkipGrid() && (float)skip_grid_min_ < isoStored()) {
-            P.cnx = (int32_t)((res_dims_[0] + 7) / 8); P.cny = (int32_t)((res_dims_[1] + 7) / 8); P.cnz = (int32_t)((res_dims_[2] + 7) / 8);
+            setSkipCells(P);
             iso_skip_grid_ = d_skip_grid_;
         }
-        const int rows = std::max(localRows(), framebuffer_size[1]);
-        const size_t n = (size_t)rows * (size_t)framebuffer_size[0];
-        if (depth_capacity_ < n) {
-            if (d_depth_) { check(hipFree(d_depth_), "hipFree(depth)"); d_depth_ = nullptr; depth_capacity_ = 0; }
-            check(hipMalloc(reinterpret_cast<void **>(&d_depth_), std::max<size_t>(n, 1) * sizeof(float)), "hipMalloc(depth)");
-            depth_capacity_ = n;
-            check(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_depth_), 0x7f800000, n, stream()), "hipMemset(depth)");   // +inf
-        }
+        growFloatTarget(d_depth_, depth_capacity_, 0x7f800000, "depth");   // +inf
         depth_rows_ = (ext_fb_ && fb_compact_) ? localRows() : framebuffer_size[1];
         depth_w_ = framebuffer_size[0];
-        tune_measure_ = false;
-        last_choice_ = 0;
+        noMeasuredChoice();
         return fb;
     }
     if (reslice_enable_) {
@@ -900,18 +912,10 @@ float4 *RendererCore::prepareLaunch(FrameParams &P, LaunchConfig &L)
         // table, speed copies or skip grid
         buildFrame(P, L);
         P.skip_empty = 0;
-        const int rows = std::max(localRows(), framebuffer_size[1]);
-        const size_t n = (size_t)rows * (size_t)framebuffer_size[0];
-        if (values_capacity_ < n) {
-            if (d_values_) { check(hipFree(d_values_), "hipFree(values)"); d_values_ = nullptr; values_capacity_ = 0; }
-            check(hipMalloc(reinterpret_cast<void **>(&d_values_), std::max<size_t>(n, 1) * sizeof(float)), "hipMalloc(values)");
-            values_capacity_ = n;
-            check(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_values_), 0x7fc00000, n, stream()), "hipMemset(values)");   // quiet NaN
-        }
+        growFloatTarget(d_values_, values_capacity_, 0x7fc00000, "values");   // quiet NaN
         values_rows_ = (ext_fb_ && fb_compact_) ? localRows() : framebuffer_size[1];
         values_w_ = framebuffer_size[0];
-        tune_measure_ = false;
-        last_choice_ = 0;
+        noMeasuredChoice();
         return fb;
     }
     if (shadeFrame()) {
@@ -923,12 +927,11 @@ float4 *RendererCore::prepareLaunch(FrameParams &P, LaunchConfig &L)
         shade_skip_grid_ = nullptr;
         int thresh = 0;
         if (skip_empty && zeroAlphaThreshold(P, filter == 1, thresh) && ensureSkipGrid() && thresh >= (int)skip_grid_min_) {
-            P.cnx = (int32_t)((res_dims_[0] + 7) / 8); P.cny = (int32_t)((res_dims_[1] + 7) / 8); P.cnz = (int32_t)((res_dims_[2] + 7) / 8);
+            setSkipCells(P);
             shade_skip_grid_ = d_skip_grid_;
             shade_skip_thresh_ = thresh;
         }
-        tune_measure_ = false;
-        last_choice_ = 0;
+        noMeasuredChoice();
         return fb;
     }
     if (filter == 1) warmTrilinear();          // (a caller that set the public field directly; a no-op once done)
@@ -963,76 +966,26 @@ void RendererCore::launch(uint32_t *spp)
     LaunchConfig L;
     float4 *fb = prepareLaunch(P, L);
     // a measurement launch of the work model: events around the kernel, read later without blocking (tuneCollect)
-    const bool measure = tune_measure_ && spp == nullptr && tune_count_ < kTuneSlots;
+    const LaunchTuner::Pick pick = tune_pick_;
+    tune_pick_ = {};
+    const bool measure = pick.measure && spp == nullptr && tune_count_ < kTuneSlots;
     TuneSlot &slot = tune_slot_[(tune_head_ + tune_count_) % kTuneSlots];
     if (measure) check(hipEventRecord(slot.ev0, stream()), "hipEventRecord");
     check(launchKernel(P, L, fb, spp), "raymarch launch");
     if (measure) {
         check(hipEventRecord(slot.ev1, stream()), "hipEventRecord");
-        slot.key = tune_key_; slot.cand = tune_cand_; slot.gen = tune_gen_;
+        slot.key = pick.key; slot.cand = pick.cand; slot.gen = pick.gen;
         tune_count_++;
-        tuneIssued(tune_key_, tune_gen_, tune_cand_);                   // counted only now that its events are on the stream
+        tuner_.issued(pick.key, pick.gen, pick.cand);                    // counted only now that its events are on the stream
     }
-    tune_measure_ = false;
 }
 
 // TRILINEAR on 16-bit volumes: whole brick layers are the first guess -- and the per-axis copies are not built -- only while the
 // central ray keeps this share of its length along one volume axis: at 0.973 (a fifth of a voxel of shear per voxel) the
 // per-tile layer thickness already wins, 1.33 against 1.46 ms on cfg3; at 1.0 whole layers do, 1.17 against 1.20
 static constexpr double kTriWholeLayerAlignment = 0.985;
-// TRILINEAR: the small tile shape (16x16 pixels, four wavefronts, 40 KiB) is the FIRST GUESS where a tile's brick layers are small
-// against its ring -- volumes up to 640 voxels along every axis (cfg1 shape 0.138 -> 0.118 ms, cfg2 shape 0.402 -> 0.381) -- and a
-// CANDIDATE of the measured choice everywhere: on 1024^3 volumes it loses at the default pose (u16 1.12 -> 1.22 ms) and at strongly
-// oblique ones (zenith 60 / azimuth 45: 1.55 -> 2.75), but wins over most of an orbit (u8: 0.92-1.02 against 1.01-1.11 ms at five of
-// seven poses; u16 with the per-axis copies: 1.22 / 1.31 / 1.22 against 1.36 / 1.40 / 1.31; profiles/r06_trilinear_orbit.txt) -- which
-// pose does which is exactly what the measurement is for.
-static bool tri_small_tiles_offered(const FrameParams &P, const LaunchConfig &L, unsigned tile_active)
-{
-    (void)P; (void)tile_active;
-    return L.tile_table_small != nullptr;
-}
 
-// ---- the measured work model.  Which kernel is fastest for a launch depends on how many tiles have work, how long
-// their rays are, how early they end and how oblique the view is (tools/config_sweep.py: the relay kernel wins a
-// 1024^3 shard with 171 active tiles by 25 %, loses a 256^3 frame with 560 by 45 %).  Round 2 chose by tile-count
-// thresholds fitted on one configuration; here the launch is MEASURED: all candidates render identical bits, so the
-// first frames of a configuration try them in turn (the heuristic's choice first), a few times each, and the fastest
-// is kept.  Keyed by everything that shapes the launch; the pose enters through the view's axis alignment and the
-// number of active tiles (buckets), so an orbiting camera re-uses what it has learnt.
-void RendererCore::tuneIssued(uint64_t key, uint64_t gen, int cand_value)
-{
-    auto it = tune_.find(key);
-    if (it == tune_.end() || it->second.gen != gen) return;
-    for (int c = 0; c < it->second.ncand; c++) if (it->second.cand[c] == cand_value) { it->second.issued[c]++; return; }
-}
-
-// `cand_value` is the candidate's bit set, `gen` the entry's generation when the measurement was launched: an entry that was
-// evicted and re-created for the same key has another shuffled order (an index would credit the wrong candidate), and a
-// result launched before a re-validation must not count towards it (round-4 advisor)
-void RendererCore::tuneRecord(uint64_t key, uint64_t gen, int cand_value, float ms)
-{
-    auto it = tune_.find(key);
-    if (it == tune_.end() || it->second.gen != gen) return;
-    int cand = -1;
-    for (int c = 0; c < it->second.ncand; c++) if (it->second.cand[c] == cand_value) cand = c;
-    if (cand < 0) return;
-    TuneEntry &e = it->second;
-    e.best_ms[cand] = e.tries[cand] == 0 ? ms : std::min(e.best_ms[cand], ms);
-    e.tries[cand]++;
-    bool all = true;
-    for (int c = 0; c < e.ncand; c++) all = all && e.tries[c] >= kTuneTries;
-    if (all) {
-        // the heuristic's choice wins ties: a rival has to be 2 % faster, more than two event timings of one kernel differ by
-        int heur = 0;
-        for (int c = 0; c < e.ncand; c++) if (e.cand[c] == e.heur) heur = c;
-        int best = heur;
-        for (int c = 0; c < e.ncand; c++)
-            if (c != heur && e.best_ms[c] < e.best_ms[best] * (best == heur ? 0.98f : 1.0f)) best = c;
-        e.settled = best;
-        e.frames_settled = 0;
-    }
-}
-
+// ---- the measured work model (launch_tuner.cpp): the results of the measurement launches whose events have completed
 void RendererCore::tuneCollect()
 {
     while (tune_count_ > 0) {                                            // the stream completes them in order
@@ -1043,7 +996,7 @@ void RendererCore::tuneCollect()
         tune_count_--;
         if (q != hipSuccess) { (void)hipGetLastError(); continue; }
         float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, s.ev0, s.ev1) == hipSuccess) tuneRecord(s.key, s.gen, s.cand, ms);
+        if (hipEventElapsedTime(&ms, s.ev0, s.ev1) == hipSuccess) tuner_.record(s.key, s.gen, s.cand, ms);
         else (void)hipGetLastError();
     }
 }
@@ -1054,9 +1007,6 @@ void RendererCore::tuneCollect()
 #define VR_BUILD_ID 0ull
 #endif
 namespace {
-struct ChoiceHeader { char magic[8]; uint32_t version, count; uint64_t build_id; char device[64]; };
-struct ChoiceRecord { uint64_t key; int32_t ncand, settled_value, heur, cand[8]; };
-static_assert(sizeof(ChoiceHeader) == 88 && sizeof(ChoiceRecord) == 56, "blob layout");
 void choiceDeviceName(int device, char (&out)[64])
 {
     // the device MODEL as a string of attributes, not hipDeviceProp_t::name: under rocprofv3 hipGetDeviceProperties came back
@@ -1077,75 +1027,34 @@ void choiceDeviceName(int device, char (&out)[64])
 }
 }  // namespace
 
+// (the blob's layout -- ChoiceHeader, ChoiceRecord -- and what an import accepts: launch_tuner.h / launch_tuner.cpp)
 size_t RendererCore::exportChoices(void *buf, size_t capacity)
 {
-    static_assert(kTuneCand == 8, "ChoiceRecord::cand");
     tuneCollect();                                                       // measurements whose events have completed since the last launch count
-    uint32_t n = 0;
-    for (const auto &kv : tune_) if (kv.second.settled >= 0) n++;
-    const size_t need = sizeof(ChoiceHeader) + (size_t)n * sizeof(ChoiceRecord);
-    if (!buf || capacity < need) return need;
-    ChoiceHeader h;
-    std::memset(&h, 0, sizeof(h));
-    std::memcpy(h.magic, "VRCHOICE", 8);
-    h.version = 1; h.count = n; h.build_id = (uint64_t)VR_BUILD_ID;
-    choiceDeviceName(device_, h.device);
-    std::memcpy(buf, &h, sizeof(h));
-    char *q = static_cast<char *>(buf) + sizeof(h);
-    for (const auto &kv : tune_) {
-        const TuneEntry &e = kv.second;
-        if (e.settled < 0) continue;
-        ChoiceRecord r;
-        std::memset(&r, 0, sizeof(r));
-        r.key = kv.first; r.ncand = e.ncand; r.settled_value = e.cand[e.settled]; r.heur = e.heur;
-        for (int c = 0; c < e.ncand; c++) r.cand[c] = e.cand[c];
-        std::memcpy(q, &r, sizeof(r));
-        q += sizeof(r);
-    }
-    return need;
+    char device[64];
+    choiceDeviceName(device_, device);
+    return tuner_.exportChoices(buf, capacity, (uint64_t)VR_BUILD_ID, device);
 }
 
 int RendererCore::importChoices(const void *buf, size_t bytes)
 {
-    if (!buf || bytes < sizeof(ChoiceHeader)) throw std::invalid_argument("importChoices: blob too short");
-    ChoiceHeader h;
-    std::memcpy(&h, buf, sizeof(h));
-    if (std::memcmp(h.magic, "VRCHOICE", 8) != 0 || h.version != 1) throw std::invalid_argument("importChoices: not a choices blob of this library");
-    if (bytes < sizeof(h) + (size_t)h.count * sizeof(ChoiceRecord)) throw std::invalid_argument("importChoices: truncated blob");
-    char mine[64];
-    choiceDeviceName(device_, mine);
-    if (h.build_id != (uint64_t)VR_BUILD_ID || std::memcmp(h.device, mine, sizeof(mine)) != 0) return 0;   // measured elsewhere: not trusted
-    const char *q = static_cast<const char *>(buf) + sizeof(h);
-    int accepted = 0;
-    for (uint32_t i = 0; i < h.count && tune_.size() < (size_t)kTuneEntries; i++, q += sizeof(ChoiceRecord)) {
-        ChoiceRecord r;
-        std::memcpy(&r, q, sizeof(r));
-        if (r.ncand < 2 || r.ncand > kTuneCand) continue;
-        int settled = -1;
-        for (int c = 0; c < r.ncand; c++) if (r.cand[c] == r.settled_value) settled = c;
-        if (settled < 0) continue;
-        TuneEntry e;
-        e.ncand = r.ncand; e.heur = r.heur; e.settled = settled;
-        for (int c = 0; c < r.ncand; c++) { e.cand[c] = r.cand[c]; e.tries[c] = e.issued[c] = kTuneTries; }
-        e.revalidated = true;                                            // it was measured at sustained clocks where it came from
-        e.last_use = tune_clock_;
-        e.gen = ++tune_gen_counter_;
-        tune_[r.key] = e;
-        accepted++;
-    }
-    return accepted;
+    char device[64];
+    choiceDeviceName(device_, device);
+    return tuner_.importChoices(buf, bytes, (uint64_t)VR_BUILD_ID, device);
 }
 
+// the measured choice of this launch: the candidate kernels it could run (the part that needs the kernels' eligibility rules),
+// the tuner's pick among them (launch_tuner.cpp) applied to L
 void RendererCore::tuneChoose(const FrameParams &P, LaunchConfig &L)
 {
-    tune_measure_ = false;
+    tune_pick_ = {};
     tuneCollect();
     const int prior = L.filter == 1 ? (L.tri_slab << 3) : ((L.sparse_shard ? 1 : 0) | (L.pipelined ? 2 : 0) | (L.short_batches ? 4 : 0));
     last_choice_ = prior;
     if (!autotune || force_generic != 0 || !L.tile_table) return;
     // candidates, the heuristic's choice (what buildFrame / refreshTileSchedule left in L) first
-    int cand[kTuneCand], n = 0;
-    auto add = [&](int c) { for (int k = 0; k < n; k++) if (cand[k] == c) return; if (n < kTuneCand) cand[n++] = c; };
+    int cand[LaunchTuner::kTuneCand], n = 0;
+    auto add = [&](int c) { for (int k = 0; k < n; k++) if (cand[k] == c) return; if (n < LaunchTuner::kTuneCand) cand[n++] = c; };
     if (fast_path_eligible(P, L)) {
         const bool relay_ok = !L.big_offsets && !(P.skip_empty != 0 && L.skip_grid != nullptr);
         add(prior & (relay_ok ? 7 : 6));
@@ -1157,8 +1066,14 @@ void RendererCore::tuneChoose(const FrameParams &P, LaunchConfig &L)
         add(prior);
         add(1 << 3);
         add(5 << 3);                                                     // three workgroups per CU: wins where the tiles' layers fit 53 KiB
-        // 16x16-pixel tiles on four wavefronts: launches whose 32x16-pixel tiles leave workgroup slots empty (two per CU)
-        if (tri_small_tiles_offered(P, L, tile_active_)) add(6 << 3);
+        // 16x16-pixel tiles on four wavefronts: launches whose 32x16-pixel tiles leave workgroup slots empty (two per CU).
+        // TRILINEAR: the small tile shape (16x16 pixels, four wavefronts, 40 KiB) is the FIRST GUESS where a tile's brick layers are small
+        // against its ring -- volumes up to 640 voxels along every axis (cfg1 shape 0.138 -> 0.118 ms, cfg2 shape 0.402 -> 0.381) -- and a
+        // CANDIDATE of the measured choice everywhere: on 1024^3 volumes it loses at the default pose (u16 1.12 -> 1.22 ms) and at strongly
+        // oblique ones (zenith 60 / azimuth 45: 1.55 -> 2.75), but wins over most of an orbit (u8: 0.92-1.02 against 1.01-1.11 ms at five of
+        // seven poses; u16 with the per-axis copies: 1.22 / 1.31 / 1.22 against 1.36 / 1.40 / 1.31; profiles/r06_trilinear_orbit.txt) -- which
+        // pose does which is exactly what the measurement is for.
+        if (L.tile_table_small != nullptr) add(6 << 3);
         if (tri_path_candidate(P, L)) add(0);
         if (L.apron_y != nullptr && L.apron_x != nullptr) {
             add(3 << 3);
@@ -1168,98 +1083,12 @@ void RendererCore::tuneChoose(const FrameParams &P, LaunchConfig &L)
         }
     }
     if (n < 2) return;
-    uint64_t key = tileScheduleKey(P, launch_local_rows(P), false);
-    auto mix = [&](uint64_t v) { key ^= v + 0x9E3779B97F4A7C15ull + (key << 6) + (key >> 2); };
-    mix((uint64_t)(viewAxisAlignment(P) * 25.0));
-    if (L.filter == 1) {
-        // the staged trilinear kernel's time follows how many tiles' brick layers fit its ring, i.e. HOW the view is oblique
-        // (orbit poses of one alignment bucket: 1.2 ... 2.5 ms on a 1024^3 u8 volume): both direction ratios, in eighths
-        double r1, r2;
-        viewAxisRatios(P, r1, r2);
-        mix((uint64_t)(r1 * 8.0) << 8 | (uint64_t)(r2 * 8.0));
-    }
-    mix((uint64_t)(std::log2((double)std::max(tile_active_, 1u)) * 3.0));
-    // opacity and window enter in coarse buckets (how early rays end, how wide the classification table is): a slider dragged
-    // through hundreds of values stays in one or two entries instead of opening a new one -- and a new exploration -- per frame
-    const double a = (double)P.alpha_scale;
-    mix((uint64_t)(a >= 0.5 ? 1000 : (a > 0.0 ? (int)std::floor(std::log2(a) * 0.5) + 500 : 0)));
-    mix((uint64_t)std::floor(std::log2((double)std::max(P.max_val - P.min_val, 1))) << 8 | (uint64_t)(L.use_lut != 0) << 1 | (uint64_t)(L.lut_noclamp != 0));
-    mix((uint64_t)P.nx << 40 | (uint64_t)P.ny << 20 | (uint64_t)P.nz);
-    mix((uint64_t)L.filter | (uint64_t)L.mip << 1 | (uint64_t)(P.tf_len > 1) << 2 | (uint64_t)(P.skip_empty != 0) << 3 | (uint64_t)L.layout << 4 |
-        (uint64_t)L.bytes_per_voxel << 5 | (uint64_t)(L.packed12 != nullptr) << 8 | (uint64_t)(L.apron != nullptr) << 9 | (uint64_t)P.fb_format << 10 |
-        (uint64_t)P.view_top << 11 | (uint64_t)P.view_bottom << 12 | (uint64_t)(L.apron_y != nullptr) << 13 | (uint64_t)prior << 16);
-    tune_clock_++;
-    tune_same_key_run_ = key == tune_last_key_ ? tune_same_key_run_ + 1 : 0;
-    tune_last_key_ = key;
-    auto it = tune_.find(key);
-    if (it == tune_.end()) {
-        // a configuration that is only passing through (an orbiting camera crossing a pose bucket, a slider crossing an opacity
-        // bucket) gets the heuristic's choice; exploring starts when the same key has come three times in a row
-        if (tune_same_key_run_ < 2) return;
-        if (tune_.size() >= (size_t)kTuneEntries) {                      // evict the least recently used eighth
-            std::vector<std::pair<uint64_t, uint64_t>> age;
-            age.reserve(tune_.size());
-            for (auto &kv : tune_) age.emplace_back(kv.second.last_use, kv.first);
-            std::nth_element(age.begin(), age.begin() + kTuneEntries / 8, age.end());
-            for (int k = 0; k < kTuneEntries / 8; k++) tune_.erase(age[(size_t)k].second);
-        }
-        it = tune_.emplace(key, TuneEntry{}).first;
-        TuneEntry &e = it->second;
-        e.ncand = n;
-        e.gen = ++tune_gen_counter_;
-        for (int k = 0; k < n; k++) e.cand[k] = cand[k];
-        e.heur = cand[0];
-        // shuffled measuring order (Fisher-Yates on a counter-seeded LCG)
-        uint64_t r = key ^ (tune_clock_ * 0x9E3779B97F4A7C15ull);
-        for (int k = n - 1; k > 0; k--) {
-            r = r * 6364136223846793005ull + 1442695040888963407ull;
-            std::swap(e.cand[k], e.cand[(int)((r >> 33) % (uint64_t)(k + 1))]);
-        }
-    }
-    TuneEntry &e = it->second;
-    e.last_use = tune_clock_;
-    int use;
-    if (e.settled >= 0) {
-        use = e.settled;
-        // one re-measurement at sustained clocks: whatever settled during the clock ramp is checked again, once
-        if (!e.revalidated && ++e.frames_settled >= kTuneRevalidateFrames) {
-            e.revalidated = true;
-            for (int c = 0; c < e.ncand; c++) { e.tries[c] = 0; e.issued[c] = 0; e.best_ms[c] = 0.0f; }
-            e.settled = -1;
-            e.next = 0;
-            e.gen = ++tune_gen_counter_;                                 // results still in flight belong to the old generation
-        }
-    } else {
-        // the next candidate that still needs a measurement launched; when every measurement is in flight (a burst of
-        // asynchronous frames) or every event pair is taken: the best so far, the heuristic's choice before any result
-        int pick = -1;
-        if (tune_count_ < kTuneSlots)
-            for (int k = 0; k < e.ncand && pick < 0; k++) {
-                const int c = (e.next + k) % e.ncand;
-                if (e.issued[c] < kTuneTries) pick = c;
-            }
-        if (pick >= 0) {
-            use = pick;
-            e.next = (pick + 1) % e.ncand;
-            // issued[] is counted where the event pair is really recorded (launch / render): a launch that cannot measure
-            // (the instrumented sample count, every slot taken) leaves the candidate to be picked again
-            tune_measure_ = true; tune_key_ = key; tune_cand_ = e.cand[use]; tune_gen_ = e.gen;
-        } else {
-            int best = -1;
-            for (int c = 0; c < e.ncand; c++)
-                if (e.tries[c] > 0 && (best < 0 || e.best_ms[c] < e.best_ms[best])) best = c;
-            if (best < 0)
-                for (int c = 0; c < e.ncand; c++) if (e.cand[c] == e.heur) best = c;
-            use = best < 0 ? 0 : best;
-            // a measurement whose events were lost (a failed launch) would leave the entry waiting for ever: with nothing in
-            // flight, whatever has not reported is launched again
-            if (tune_count_ == 0)
-                for (int c = 0; c < e.ncand; c++) if (e.tries[c] < kTuneTries) e.issued[c] = e.tries[c];
-        }
-    }
-    const int c = e.cand[use];
+    const uint64_t key = launchTuneKey(P, L, launch_local_rows(P), tile_active_, prior);
+    tune_pick_ = tuner_.choose(key, cand, n, tune_count_, kTuneSlots);
+    if (!tune_pick_.decided) return;                                     // only passing through: L and last_choice_ stay the heuristics'
+    const int c = tune_pick_.cand;
     L.sparse_shard = (c & 1) ? 1 : 0; L.pipelined = (c & 2) ? 1 : 0; L.short_batches = (c & 4) ? 1 : 0; L.tri_slab = (c >> 3) & 15;
-    last_choice_ = c | (e.settled < 0 ? 256 : 0);                        // bit 8: a trial frame of a configuration still being explored
+    last_choice_ = c | (tune_pick_.trial ? 256 : 0);                     // bit 8: a trial frame of a configuration still being explored
 }
 
 // 12-bit packed copy (vr_set_pack12, default on): when the voxels of a bricked u16 volume span at most 4096
@@ -1649,10 +1478,8 @@ void RendererCore::render()
     FrameParams P;
     LaunchConfig L;
     float4 *fb = prepareLaunch(P, L);
-    const bool measure = tune_measure_;
-    const uint64_t mkey = tune_key_, mgen = tune_gen_;
-    const int mcand = tune_cand_;
-    tune_measure_ = false;
+    const LaunchTuner::Pick pick = tune_pick_;
+    tune_pick_ = {};
     check(hipEventRecord(ev0_, stream()), "hipEventRecord");
     check(launchKernel(P, L, fb, nullptr), "raymarch launch");
     check(hipEventRecord(ev1_, stream()), "hipEventRecord");
@@ -1660,7 +1487,7 @@ void RendererCore::render()
     float ms = 0.0f;
     check(hipEventElapsedTime(&ms, ev0_, ev1_), "hipEventElapsedTime");
     kerneltime_sum += ms;
-    if (measure) { tuneIssued(mkey, mgen, mcand); tuneRecord(mkey, mgen, mcand, ms); }   // the blocking path measures anyway
+    if (pick.measure) { tuner_.issued(pick.key, pick.gen, pick.cand); tuner_.record(pick.key, pick.gen, pick.cand, ms); }   // the blocking path measures anyway
 }
 
 hipError_t RendererCore::launchKernel(const FrameParams &P, const LaunchConfig &L, float4 *fb, uint32_t *spp)

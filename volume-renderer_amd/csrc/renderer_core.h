@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "camera.h"
+#include "launch_tuner.h"
 #include "vr_frame.h"
 
 namespace vr {
@@ -266,40 +267,18 @@ private:
     void refreshTileSchedule(const FrameParams &P, LaunchConfig &L);
     const char *last_kernel_ = "";
     bool tslab_warm_ = false;
-    // ---- measured work model (kernel variant 0): every candidate kernel of a configuration renders the same bits, so
-    // the first frames of a configuration double as measurements -- each candidate is timed a few times (HIP events on
-    // the launch stream, polled without blocking), the fastest is kept until the configuration changes.
-    // A candidate = bit set: 1 relay kernel, 2 pipelined batch loop, 4 four-sample batches; bits 3 .. 6: LaunchConfig::tri_slab
-    // (0 = batched trilinear kernel, 1 / 3 / 4 = the LDS-staged kernel in one of its shapes).
-    // An entry settles on the fastest candidate after kTuneTries measurements of each (in an order shuffled per entry, so no
-    // candidate is always the one measured on cold clocks), is measured ONCE more kTuneRevalidateFrames frames later (the first
-    // ~25 frames after idle run ~15 % slow while the clocks ramp) and is evicted least-recently-used first.
-    static constexpr int kTuneCand = 8, kTuneTries = 2, kTuneRevalidateFrames = 96, kTuneEntries = 512;
-    struct TuneEntry {
-        int ncand = 0, cand[kTuneCand] = {}, tries[kTuneCand] = {}, issued[kTuneCand] = {}, settled = -1, next = 0;   // issued: measurements launched (a burst of asynchronous frames launches kTuneTries per candidate, not one per frame until the results arrive)
-        int heur = 0;                        // the heuristic's choice (a candidate value): it wins ties
-        float best_ms[kTuneCand] = {};
-        int frames_settled = 0;              // launches since it settled
-        bool revalidated = false;
-        uint64_t last_use = 0;               // launch counter at its last use (eviction order)
-        uint64_t gen = 0;                    // generation: results of measurements launched for an earlier life of this key (evicted and re-created, or before a re-validation) are dropped
-    };
-    std::map<uint64_t, TuneEntry> tune_;
+    // ---- measured work model (kernel variant 0; launch_tuner.h): the tuner decides which candidate kernel a launch runs, this
+    // class enumerates the candidates and times the measurement launches (HIP events on the launch stream, polled without blocking)
+    LaunchTuner tuner_;
     static constexpr int kTuneSlots = 12;    // asynchronous measurements that may be in flight (a burst of renderAsync calls)
     struct TuneSlot { hipEvent_t ev0 = nullptr, ev1 = nullptr; uint64_t key = 0, gen = 0; int cand = -1; };   // cand: the candidate VALUE (bit set), not its index in the entry's shuffled order
     TuneSlot tune_slot_[kTuneSlots];
     int tune_head_ = 0, tune_count_ = 0;     // ring of in-flight slots: oldest at tune_head_
-    bool tune_measure_ = false;              // the launch being prepared is a measurement of candidate tune_cand_ of entry tune_key_
-    uint64_t tune_key_ = 0;
-    int tune_cand_ = -1;                     // candidate VALUE being measured
-    uint64_t tune_gen_ = 0, tune_gen_counter_ = 0;
-    uint64_t tune_clock_ = 0, tune_last_key_ = 0;   // launches seen; the previous launch's key and for how many launches in a row
-    int tune_same_key_run_ = 0;
+    LaunchTuner::Pick tune_pick_;            // the tuner's decision for the launch being prepared (measure: it is a measurement)
     int last_choice_ = 0;                    // candidate bits of the last launch (vr_get_launch_choice)
     void tuneChoose(const FrameParams &P, LaunchConfig &L);
-    void tuneRecord(uint64_t key, uint64_t gen, int cand, float ms);
-    void tuneIssued(uint64_t key, uint64_t gen, int cand);   // a measurement of `cand` was really launched (events recorded)
     void tuneCollect();
+    void noMeasuredChoice() { tune_pick_ = {}; last_choice_ = 0; }   // a frame of a mode with one kernel (isosurface, reslice, shaded)
 
     hipStream_t stream() const { return user_stream_ ? user_stream_ : own_stream_; }
     void requireDevice(const char *what) const;
@@ -315,6 +294,8 @@ private:
     bool certifyDivisor(float b);
     void buildFrame(FrameParams &P, LaunchConfig &L);
     float4 *prepareLaunch(FrameParams &P, LaunchConfig &L);
+    void setSkipCells(FrameParams &P) const;
+    void growFloatTarget(float *&d, size_t &capacity, int fill, const char *name);
     void launch(uint32_t *spp);
     void updateWorkgroups();
     void setMessage(const std::string &t, const std::string &m) { title = t; msg = m; }
