@@ -296,6 +296,63 @@ int vr_set_smoothing_workspace(vr_handle h, uint64_t bytes);
 /* measurement aid: HIP-event time, in ms, of the passes of the last vr_smooth_volume that ran any (first launch to last,
    every slab; allocations, the range scan and host work excluded); 0 before the first and after a call that ran none */
 int vr_get_smoothing_ms(vr_handle h, float *ms);
+/* Extraction of the isosurface s = iso of the resident volume -- the one being rendered, i.e. the smoothed one after
+   vr_smooth_volume -- as a watertight indexed triangle mesh, computed on the device (no reference equivalent): positions in
+   the units of vr_get_dims' spacing, unit normals, uint32 triangle indices.  Marching tetrahedra on the Kuhn (six-tetrahedra)
+   split of every voxel cell: no ambiguous cases, so the surface is edge-manifold by construction.  The surface is open where
+   it meets the volume's boundary; caps are out of scope.  Every step is one correctly rounded fp32 operation in the order
+   given, nothing contracted:
+   1. Lattice: voxel (i, j, k) is a lattice point, x the fastest axis.  A cell is the cube between (i, j, k) and
+      (i+1, j+1, k+1): (nx-1)(ny-1)(nz-1) cells.  Any dimension below 2: no cells, the mesh is empty (0 vertices, 0 triangles)
+      and the call succeeds.
+   2. Values: s = (float) of the raw stored voxel.  iso_s = float(iso_value + 1000) for 16-bit data under
+      VR_QUIRK_U16_OFFSET, float(iso_value) otherwise (vr_set_isosurface's rule: both show the same surface).  A voxel is
+      INSIDE when s >= iso_s.
+   3. Edges: the seven directions e_0 .. e_6 = (1,0,0), (0,1,0), (0,0,1), (1,1,0), (1,0,1), (0,1,1), (1,1,1).  Edge (A, d)
+      runs from voxel A to B = A + e_d and exists when B lies in the volume.  It carries a vertex when exactly one of A and B
+      is inside.
+   4. Vertex: f = (iso_s - s_A) / (s_B - s_A) (two subtractions, one division; f lies in [0, 1]).  Per axis a:
+      p_a = ((float)A_a + f) * spacing_a where e_d has a 1 on that axis, (float)A_a * spacing_a where it has a 0: voxel
+      (0,0,0)'s centre is the origin.  f = 0 (s_A == iso_s) makes vertices coincide; the zero-area triangles are kept.
+   5. Normal: g(V)_a = S(min(V_a+1, dim_a-1)) - S(max(V_a-1, 0)) at voxel indices (the isosurface mode's NEAREST gradient);
+      G_a = g(A)_a + f * (g(B)_a - g(A)_a) (difference, product, sum); H_a = G_a / spacing_a; v = -H;
+      dot = (v_z*v_z + v_y*v_y) + v_x*v_x; N = v * (1.0f / sqrtf(dot)), (0,0,0) when dot == 0.  It points to lower values,
+      out of bright objects.
+   6. Vertex order: by the owner voxel A's linear index i + nx*(j + ny*k), then by d.
+   7. Tetrahedra: for the axis permutations pi in the order xyz, xzy, yxz, yzx, zxy, zyx, tetrahedron t has the corners
+      c_0 = (0,0,0), c_1 = c_0 + e_pi1, c_2 = c_1 + e_pi2, c_3 = (1,1,1) relative to the cell.  Every tetrahedron edge
+      c_n -> c_m (n < m) is edge (cell + c_n, direction c_m - c_n) of step 3: vertices are shared between tetrahedra and cells.
+   8. Cases: m = the mask of inside corners (bit n: c_n); I, O = the inside, outside corners in ascending order; xy = the
+      vertex on the tetrahedron edge between corners x and y.  |I| = 1, a = I_0: triangle (aO_0, aO_1, aO_2).  |I| = 3,
+      a = O_0: (aI_0, aI_1, aI_2).  |I| = 2, I = (a, b), O = (c, d): (ac, ad, bd) and (ac, bd, bc).  m = 0, 15: none.
+   9. Winding: the second and third vertex of every triangle of an entry (t, m) are swapped when, with the vertices at the
+      edge midpoints in lattice coordinates, (v_1 - v_0) x (v_2 - v_0) . (mean of O - mean of I) < 0 for its first triangle:
+      the front face, counter-clockwise, is seen from the outside.  Check value: the even permutations xyz, yzx, zxy swap
+      exactly m in {2, 5, 8, 10, 11, 14}, the odd ones the other eight cases.
+   10. Triangle order: by the cell's linear index i + (nx-1)*(j + (ny-1)*k), then t, then the order within the case.
+   The mesh is a snapshot on the device: it stays valid until the next extraction, vr_free_mesh or vr_destroy, survives
+   loading or smoothing another volume, and counts under `other` in vr_get_resident_bytes.  An extraction changes no
+   rendering state (window, modes, launch choices, copies, stream) and queues no message on success.  Errors: no volume:
+   VR_E_INVALID; a host-only handle: VR_E_NO_DEVICE; more than 2^32 - 1 vertices or triangles: VR_E_INVALID and a message for
+   vr_take_message; a device allocation that fails: VR_E_NOMEM; after any of them the previous mesh is still there.
+   vr_get_mesh_info, vr_read_mesh and vr_save_mesh before the first mesh, a capacity (in vertices, triangles) that is too
+   small, an unknown extension: VR_E_INVALID.  n_vertices, n_triangles and any pointer of vr_read_mesh may be NULL.
+   vr_save_mesh: ext "stl" = binary STL (80-byte header that does not begin with `solid`, uint32 count, 50 bytes a triangle;
+   the facet normal is the unit cross product of the stored positions computed in double, (0,0,0) for a zero-area triangle;
+   attribute word 0); "ply" = binary_little_endian 1.0, vertex properties x y z nx ny nz as float, faces uchar uint.
+   Work arrays (9 bytes a voxel) are bounded by vr_set_mesh_workspace (0, the default: 2 GiB or what the device has free):
+   the extraction runs in z slabs that fit, and the mesh is the same bytes for every slab size and on every run.  A bound
+   below two planes gives VR_E_NOMEM. */
+int vr_extract_isosurface(vr_handle h, int32_t iso_value, uint64_t *n_vertices, uint64_t *n_triangles);
+int vr_get_mesh_info(vr_handle h, int32_t *iso_value, uint64_t *n_vertices, uint64_t *n_triangles);
+int vr_read_mesh(vr_handle h, float *positions, float *normals, uint32_t *triangles,
+                 uint64_t vertex_capacity, uint64_t triangle_capacity);
+int vr_save_mesh(vr_handle h, const char *path, const char *ext);
+int vr_free_mesh(vr_handle h);
+int vr_set_mesh_workspace(vr_handle h, uint64_t bytes);
+/* measurement aid: HIP-event time, in ms, of the kernels of the last successful vr_extract_isosurface (the counting pass plus
+   the emitting pass; allocations and host work excluded); 0 before the first */
+int vr_get_mesh_ms(vr_handle h, float *ms);
 /* kernel selection: 0 = automatic (specialised kernels when the configuration allows; launches far from filling the
    chip -- fewer than 256 active 32x16 tiles, 1024 when the view is oblique to the volume axes -- use the 4-wavefront
    relay kernel; the fast kernel runs its software-pipelined batch loop unless alpha_scale >= 0.5),

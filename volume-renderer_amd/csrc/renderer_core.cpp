@@ -19,6 +19,7 @@
 #include "vr_reslice.h"
 #include "vr_shade.h"
 #include "vr_smooth.h"
+#include "vr_mesh.h"
 #include "vr_kernels.h"
 
 namespace vr {
@@ -50,6 +51,7 @@ RendererCore::~RendererCore()
         (void)hipSetDevice(device_);
         (void)hipStreamSynchronize(stream());
         freeVolume();
+        freeMesh();
         if (d_fb_) (void)hipFree(d_fb_);
         if (d_tf_) (void)hipFree(d_tf_);
         if (d_tile_table_) (void)hipFree(d_tile_table_);
@@ -174,6 +176,7 @@ bool RendererCore::loadShader(std::string fn, bool reload)
         check(launch_warm_reslice(stream()), "module pre-load (reslice)");
         check(launch_warm_shade(stream()), "module pre-load (shading)");
         check(launch_warm_smooth(stream()), "module pre-load (smoothing)");
+        check(launch_warm_mesh(stream()), "module pre-load (extraction)");
         check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
         tslab_warm_ = false;
         if (filter == 1) warmTrilinear();
@@ -500,6 +503,212 @@ void RendererCore::smoothVolume(float sigma_x, float sigma_y, float sigma_z)
     }
     for (int a = 0; a < 3; a++) smooth_sigma_[a] = sigma[a];
     dropDerived();                                                       // what a load leaves behind for new voxels
+}
+
+// ---------------------------------------------------------------- extraction (vr_extract_isosurface)
+uint64_t RendererCore::meshBytes() const { return mesh_nv_ * 24 + mesh_nt_ * 12; }
+
+void RendererCore::freeMesh()
+{
+    if (d_mesh_pos_) (void)hipFree(d_mesh_pos_);
+    if (d_mesh_nrm_) (void)hipFree(d_mesh_nrm_);
+    if (d_mesh_tri_) (void)hipFree(d_mesh_tri_);
+    d_mesh_pos_ = d_mesh_nrm_ = nullptr; d_mesh_tri_ = nullptr;
+    mesh_nv_ = mesh_nt_ = 0;
+    mesh_valid_ = false;
+}
+
+// Two passes over the z slabs the workspace allows.  The first counts and scans every slab and keeps only the slabs' totals: the
+// mesh's size is known, and checked, before anything of it is allocated.  The second counts and scans a slab again (not where one
+// slab is the whole volume: its arrays are still there) and emits its vertices and triangles at the bases the totals give; a slab
+// without a vertex is skipped.  The arrays are freed before this returns; the previous mesh is replaced only at the very end.
+void RendererCore::extractIsosurface(int32_t iso, uint64_t *n_vertices, uint64_t *n_triangles)
+{
+    requireDevice("extractIsosurface");
+    if (!d_vol_) throw std::runtime_error("extractIsosurface: no dataset loaded");
+    const int nx = res_dims_[0], ny = res_dims_[1], nz = res_dims_[2];
+    struct Scratch {                                     // device allocations of this call; hipFree waits for the kernels that use them
+        std::vector<void *> p;
+        ~Scratch() { for (void *q : p) if (q) (void)hipFree(q); }
+        void *get(size_t bytes, const char *what)
+        {
+            void *q = nullptr;
+            if (hipMalloc(&q, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                throw DeviceMemoryError(hipErrorOutOfMemory, std::string("extractIsosurface: hipMalloc(") + what + ") failed");
+            }
+            p.push_back(q);
+            return q;
+        }
+        void *release(void *q) { for (void *&r : p) if (r == q) r = nullptr; return q; }
+    } scratch;
+    uint64_t nv = 0, nt = 0;
+    float *pos = nullptr, *nrm = nullptr;
+    uint32_t *tri = nullptr;
+    float ms = 0.0f;
+    if (nx >= 2 && ny >= 2 && nz >= 2) {
+        const uint64_t plane = (uint64_t)nx * (uint64_t)ny;
+        uint64_t bound = mesh_workspace_limit;
+        if (bound == 0) {
+            bound = 2ull << 30;
+            size_t free_b = 0, total_b = 0;
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+                const uint64_t reserve = std::max<uint64_t>(kCopyReserveBytes, (uint64_t)total_b / 10);   // (what copyFits keeps free)
+                bound = std::min<uint64_t>(bound, (uint64_t)free_b > reserve ? (uint64_t)free_b - reserve : 0);
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+        // planes the arrays hold: a slab's own ones and the plane after them
+        uint64_t planes = std::min<uint64_t>(std::min<uint64_t>(bound / (kMeshBytesPerVoxel * plane), kMeshMaxSlabVoxels / plane), (uint64_t)nz);
+        if (planes < 2) throw DeviceMemoryError(hipErrorOutOfMemory, "extractIsosurface: the workspace cannot hold two planes of per-voxel counts");
+        const int slab = planes >= (uint64_t)nz ? nz : (int)planes - 1;
+        const int nslabs = (nz + slab - 1) / slab;
+        const uint64_t words = planes * plane + 1;
+        const size_t temp_bytes = mesh_scan_temp_bytes(words);
+        uint64_t *d_scan = static_cast<uint64_t *>(scratch.get(words * sizeof(uint64_t), "offsets"));
+        uint8_t *d_mask = static_cast<uint8_t *>(scratch.get(planes * plane, "masks"));
+        void *d_temp = scratch.get(temp_bytes ? temp_bytes : 16, "scan scratch");
+        uint64_t *d_totals = static_cast<uint64_t *>(scratch.get((size_t)nslabs * 2 * sizeof(uint64_t), "totals"));
+        MeshSlab S = {};
+        S.volume = d_vol_; S.bytes_per_voxel = res_bytes_; S.layout = vol_layout_;
+        S.nx = nx; S.ny = ny; S.nz = nz;
+        S.iso_s = (float)((int64_t)iso + (datasize_bytes == 2 && (quirks & kQuirkU16Offset) ? 1000 : 0));   // isoStored's rule
+        for (int a = 0; a < 3; a++) S.spacing[a] = voxel_size[a];
+        S.scan = d_scan; S.mask = d_mask;
+        auto countAndScan = [&](int s) {
+            S.z0 = s * slab; S.z1 = std::min(S.z0 + slab, nz);
+            hipError_t e = launch_mesh_count(S, stream());
+            if (e == hipSuccess) e = launch_mesh_scan(d_scan, mesh_scan_words(S), d_temp, temp_bytes, stream());
+            return e;
+        };
+        auto timed = [&](hipError_t e) {                 // the kernels between ev0_ and ev1_ (the events render() times frames with)
+            if (e == hipSuccess) e = hipEventRecord(ev1_, stream());
+            const hipError_t es = hipStreamSynchronize(stream());
+            if (e == hipSuccess) e = es;
+            float t = 0.0f;
+            if (e == hipSuccess) e = hipEventElapsedTime(&t, ev0_, ev1_);
+            ms += t;
+            return e;
+        };
+        hipError_t e = hipEventRecord(ev0_, stream());
+        for (int s = 0; s < nslabs && e == hipSuccess; s++) {
+            e = countAndScan(s);
+            // vertices of the slab's own planes: the offset of the first voxel after them; triangles: the last word's offset
+            if (e == hipSuccess) e = hipMemcpyAsync(d_totals + 2 * s, d_scan + (uint64_t)(S.z1 - S.z0) * plane, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream());
+            if (e == hipSuccess) e = hipMemcpyAsync(d_totals + 2 * s + 1, d_scan + mesh_scan_words(S) - 1, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream());
+        }
+        check(timed(e), "extraction kernels (count)");
+        std::vector<uint64_t> totals((size_t)nslabs * 2);
+        check(hipMemcpy(totals.data(), d_totals, totals.size() * sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy(D2H totals)");
+        std::vector<uint64_t> vbase((size_t)nslabs), tbase((size_t)nslabs);
+        for (int s = 0; s < nslabs; s++) {
+            vbase[s] = nv; tbase[s] = nt;
+            nv += totals[2 * s] & 0xffffffffull;
+            nt += totals[2 * s + 1] >> 32;
+        }
+        if (nv > 0xffffffffull || nt > 0xffffffffull) {
+            setMessage("Error!", "The isosurface has " + std::to_string(nv) + " vertices and " + std::to_string(nt) +
+                                     " triangles: more than 32-bit indices address. Smooth the volume or choose another iso value.");
+            throw std::invalid_argument("extractIsosurface: more than 2^32 - 1 vertices or triangles");
+        }
+        if (nv > 0) {
+            pos = static_cast<float *>(scratch.get(nv * 12, "positions"));
+            nrm = static_cast<float *>(scratch.get(nv * 12, "normals"));
+        }
+        if (nt > 0) tri = static_cast<uint32_t *>(scratch.get(nt * 12, "triangles"));
+        if (nv > 0) {
+            S.positions = pos; S.normals = nrm; S.triangles = tri;
+            e = hipEventRecord(ev0_, stream());
+            for (int s = 0; s < nslabs && e == hipSuccess; s++) {
+                if ((totals[2 * s] & 0xffffffffull) == 0) continue;
+                if (nslabs > 1) e = countAndScan(s);
+                else { S.z0 = 0; S.z1 = nz; }
+                S.vertex_base = vbase[s]; S.triangle_base = tbase[s];
+                if (e == hipSuccess) e = launch_mesh_emit(S, stream());
+            }
+            check(timed(e), "extraction kernels (emit)");
+        }
+    }
+    freeMesh();
+    d_mesh_pos_ = static_cast<float *>(scratch.release(pos));
+    d_mesh_nrm_ = static_cast<float *>(scratch.release(nrm));
+    d_mesh_tri_ = static_cast<uint32_t *>(scratch.release(tri));
+    mesh_nv_ = nv; mesh_nt_ = nt; mesh_iso_ = iso; mesh_valid_ = true;
+    last_mesh_ms_ = ms;
+    if (n_vertices) *n_vertices = nv;
+    if (n_triangles) *n_triangles = nt;
+}
+
+void RendererCore::meshInfo(int32_t *iso, uint64_t *n_vertices, uint64_t *n_triangles) const
+{
+    if (!mesh_valid_) throw std::invalid_argument("meshInfo: no isosurface has been extracted");
+    if (iso) *iso = mesh_iso_;
+    if (n_vertices) *n_vertices = mesh_nv_;
+    if (n_triangles) *n_triangles = mesh_nt_;
+}
+
+void RendererCore::readMesh(float *positions, float *normals, uint32_t *triangles, uint64_t vertex_capacity, uint64_t triangle_capacity)
+{
+    if (!mesh_valid_) throw std::invalid_argument("readMesh: no isosurface has been extracted");
+    if (((positions || normals) && vertex_capacity < mesh_nv_) || (triangles && triangle_capacity < mesh_nt_))
+        throw std::invalid_argument("readMesh: buffer too small");
+    requireDevice("readMesh");
+    if (positions && mesh_nv_) check(hipMemcpyAsync(positions, d_mesh_pos_, mesh_nv_ * 12, hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H positions)");
+    if (normals && mesh_nv_) check(hipMemcpyAsync(normals, d_mesh_nrm_, mesh_nv_ * 12, hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H normals)");
+    if (triangles && mesh_nt_) check(hipMemcpyAsync(triangles, d_mesh_tri_, mesh_nt_ * 12, hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H triangles)");
+    check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
+}
+
+// "stl": binary STL, the facet normal the unit cross product of the stored positions in double, (0, 0, 0) for a zero-area
+// triangle, attribute word 0.  "ply": binary_little_endian 1.0, x y z nx ny nz as float, faces uchar uint.
+void RendererCore::saveMesh(const std::string &fn, const std::string &ext)
+{
+    if (!mesh_valid_) throw std::invalid_argument("saveMesh: no isosurface has been extracted");
+    if (ext != "stl" && ext != "ply") throw std::invalid_argument("saveMesh: the extension must be \"stl\" or \"ply\"");
+    std::vector<float> pos((size_t)mesh_nv_ * 3), nrm((size_t)mesh_nv_ * 3);
+    std::vector<uint32_t> tri((size_t)mesh_nt_ * 3);
+    readMesh(pos.data(), ext == "ply" ? nrm.data() : nullptr, tri.data(), mesh_nv_, mesh_nt_);
+    FILE *f = std::fopen(fn.c_str(), "wb");
+    if (!f) throw IoError("saveMesh: cannot open " + fn);
+    bool ok = true;
+    auto put = [&](const void *p, size_t n) { ok = ok && (n == 0 || std::fwrite(p, 1, n, f) == n); };
+    if (ext == "stl") {
+        char header[80] = "binary STL written by vr_save_mesh";
+        const uint32_t count = (uint32_t)mesh_nt_;
+        put(header, sizeof(header));
+        put(&count, 4);
+        for (uint64_t t = 0; t < mesh_nt_ && ok; t++) {
+            const float *p0 = &pos[3 * (size_t)tri[3 * t]], *p1 = &pos[3 * (size_t)tri[3 * t + 1]], *p2 = &pos[3 * (size_t)tri[3 * t + 2]];
+            const double u[3] = {(double)p1[0] - p0[0], (double)p1[1] - p0[1], (double)p1[2] - p0[2]};
+            const double v[3] = {(double)p2[0] - p0[0], (double)p2[1] - p0[1], (double)p2[2] - p0[2]};
+            const double c[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
+            const double len = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+            float rec[12] = {};
+            if (len > 0.0) for (int a = 0; a < 3; a++) rec[a] = (float)(c[a] / len);
+            for (int a = 0; a < 3; a++) { rec[3 + a] = p0[a]; rec[6 + a] = p1[a]; rec[9 + a] = p2[a]; }
+            const uint16_t attribute = 0;
+            put(rec, sizeof(rec));
+            put(&attribute, 2);
+        }
+    } else {
+        const std::string header = "ply\nformat binary_little_endian 1.0\ncomment isosurface at " + std::to_string(mesh_iso_) +
+                                   ", written by vr_save_mesh\nelement vertex " + std::to_string(mesh_nv_) +
+                                   "\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n"
+                                   "element face " + std::to_string(mesh_nt_) + "\nproperty list uchar uint vertex_indices\nend_header\n";
+        put(header.data(), header.size());
+        for (uint64_t v = 0; v < mesh_nv_ && ok; v++) {
+            put(&pos[3 * (size_t)v], 12);
+            put(&nrm[3 * (size_t)v], 12);
+        }
+        const uint8_t three = 3;
+        for (uint64_t t = 0; t < mesh_nt_ && ok; t++) {
+            put(&three, 1);
+            put(&tri[3 * (size_t)t], 12);
+        }
+    }
+    if (std::fclose(f) != 0) ok = false;
+    if (!ok) throw IoError("saveMesh: writing " + fn + " failed");
 }
 
 // min/max scan of src/RendererCore.cpp:360-384 as a device reduction
@@ -1236,7 +1445,7 @@ void RendererCore::residentBytes(uint64_t &volume, uint64_t &copies, uint64_t &o
     copies = copiesBytes();
     const uint64_t px = (uint64_t)framebuffer_size[0] * (uint64_t)framebuffer_size[1];
     other = (d_fb_ ? px * 16 : 0) + (d_tf_ ? 256 * 16 : 0) + (uint64_t)spp_capacity_ * 4 + (d_scratch_ ? 264 * 4 : 0) +
-            (d_skip_grid_ ? (uint64_t)skip_grid_cells_ * 2 : 0) + (uint64_t)loaded_alloc_bytes_ + (uint64_t)rgba8_capacity_ + (uint64_t)present_capacity_ * kPresentSlots +
+            (d_skip_grid_ ? (uint64_t)skip_grid_cells_ * 2 : 0) + (uint64_t)loaded_alloc_bytes_ + meshBytes() + (uint64_t)rgba8_capacity_ + (uint64_t)present_capacity_ * kPresentSlots +
             ((uint64_t)tile_table_capacity_ + (uint64_t)tile_table_tall_capacity_ + (uint64_t)tile_table_small_capacity_ + (uint64_t)tile_work_capacity_) * 4;
 }
 

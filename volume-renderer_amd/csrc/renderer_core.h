@@ -145,6 +145,21 @@ public:
     // upper bound on the bytes of ONE of smoothVolume's two fp32 plane buffers (vr_set_smoothing_workspace); 0: automatic -- the
     // whole volume's planes where they fit in 2 GiB and in the free device memory, z slabs of the volume otherwise
     uint64_t smooth_workspace_limit = 0;
+    // extraction of the isosurface s = iso of the volume being rendered as an indexed triangle mesh (vr_extract_isosurface;
+    // vr_mesh.hip).  The mesh is a snapshot on the device: it stays until the next extraction, freeMesh or the handle's end, and
+    // loading or smoothing another volume leaves it alone.  No volume: std::runtime_error; more than 2^32 - 1 vertices or
+    // triangles: a queued message and std::invalid_argument; an allocation that fails: DeviceMemoryError; in each case the
+    // previous mesh stays.  No rendering state changes.
+    void extractIsosurface(int32_t iso, uint64_t *n_vertices, uint64_t *n_triangles);
+    bool hasMesh() const { return mesh_valid_; }
+    void meshInfo(int32_t *iso, uint64_t *n_vertices, uint64_t *n_triangles) const;
+    void readMesh(float *positions, float *normals, uint32_t *triangles, uint64_t vertex_capacity, uint64_t triangle_capacity);
+    void saveMesh(const std::string &fn, const std::string &ext);   // "stl" (binary) | "ply" (binary little endian)
+    void freeMesh();
+    float lastMeshMs() const { return last_mesh_ms_; }   // HIP-event time of the last extraction's kernels (the counting pass plus the emitting pass)
+    // upper bound on the bytes of extractIsosurface's per-voxel arrays (vr_set_mesh_workspace; 9 bytes a voxel); 0: automatic --
+    // 2 GiB or what the device has free; the extraction runs in z slabs that fit
+    uint64_t mesh_workspace_limit = 0;
 
     int filter = 0, accum = 0, skip_empty = 0;
     int layout = 1;          // VR_LAYOUT_BRICKED: the faster HBM layout is the default (vr_set_layout)
@@ -175,6 +190,13 @@ private:
     size_t loaded_alloc_bytes_ = 0;
     float smooth_sigma_[3] = {0.0f, 0.0f, 0.0f};
     float last_smooth_ms_ = 0.0f;
+    bool mesh_valid_ = false;                // an extraction has succeeded (its mesh may be empty) and was not freed
+    int32_t mesh_iso_ = 0;
+    uint64_t mesh_nv_ = 0, mesh_nt_ = 0;
+    float *d_mesh_pos_ = nullptr, *d_mesh_nrm_ = nullptr;   // 3 floats a vertex
+    uint32_t *d_mesh_tri_ = nullptr;         // 3 indices a triangle
+    float last_mesh_ms_ = 0.0f;
+    uint64_t meshBytes() const;              // device bytes of the mesh
     // geometry and voxel type of the volume that is RESIDENT (set only after a successful upload).
     // tex3D_dim / datasize_bytes above are GUI inputs of readVolumeData, like the reference's fields;
     // the reference's shader reads textureSize() of the uploaded texture (VolumeRenderer.cs:62), not them.

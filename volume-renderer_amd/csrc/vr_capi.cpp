@@ -387,6 +387,48 @@ int vr_set_smoothing_workspace(vr_handle h, uint64_t bytes)
     return VR_OK;
 }
 
+int vr_extract_isosurface(vr_handle h, int32_t iso_value, uint64_t *n_vertices, uint64_t *n_triangles)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.extractIsosurface(iso_value, n_vertices, n_triangles); });
+}
+
+int vr_get_mesh_info(vr_handle h, int32_t *iso_value, uint64_t *n_vertices, uint64_t *n_triangles)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.meshInfo(iso_value, n_vertices, n_triangles); });
+}
+
+int vr_read_mesh(vr_handle h, float *positions, float *normals, uint32_t *triangles, uint64_t vertex_capacity, uint64_t triangle_capacity)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.readMesh(positions, normals, triangles, vertex_capacity, triangle_capacity); });
+}
+
+int vr_save_mesh(vr_handle h, const char *path, const char *ext)
+{
+    return guarded(h, [&](vr::RendererCore &c) {
+        if (!path || !ext) throw std::invalid_argument("vr_save_mesh: null argument");
+        c.saveMesh(path, ext);
+    });
+}
+
+int vr_free_mesh(vr_handle h)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.freeMesh(); });
+}
+
+int vr_set_mesh_workspace(vr_handle h, uint64_t bytes)
+{
+    if (!h) return VR_E_INVALID;
+    h->core.mesh_workspace_limit = bytes;
+    return VR_OK;
+}
+
+int vr_get_mesh_ms(vr_handle h, float *ms)
+{
+    if (!h || !ms) return VR_E_INVALID;
+    *ms = h->core.lastMeshMs();
+    return VR_OK;
+}
+
 int vr_set_autotune(vr_handle h, int enable)
 {
     if (!h) return VR_E_INVALID;

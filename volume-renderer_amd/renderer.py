@@ -130,6 +130,13 @@ def load_library() -> C.CDLL:
         "vr_smooth_weights": (i32, [f32, C.POINTER(f32), i32, C.POINTER(i32)]),
         "vr_set_smoothing_workspace": (i32, [h, C.c_uint64]),
         "vr_get_smoothing_ms": (i32, [h, C.POINTER(f32)]),
+        "vr_extract_isosurface": (i32, [h, i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "vr_get_mesh_info": (i32, [h, C.POINTER(i32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "vr_read_mesh": (i32, [h, C.POINTER(f32), C.POINTER(f32), C.POINTER(C.c_uint32), C.c_uint64, C.c_uint64]),
+        "vr_save_mesh": (i32, [h, C.c_char_p, C.c_char_p]),
+        "vr_free_mesh": (i32, [h]),
+        "vr_set_mesh_workspace": (i32, [h, C.c_uint64]),
+        "vr_get_mesh_ms": (i32, [h, C.POINTER(f32)]),
         "vr_set_autotune": (i32, [h, i32]),
         "vr_export_choices": (i32, [h, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
         "vr_import_choices": (i32, [h, C.c_void_p, C.c_size_t, C.POINTER(i32)]),
@@ -656,6 +663,44 @@ class RendererCore:
 
     def setSmoothingWorkspace(self, nbytes):
         self._check(self._lib.vr_set_smoothing_workspace(self._h, C.c_uint64(int(nbytes))))
+
+    def extractIsosurface(self, iso):
+        """vr_extract_isosurface: the surface s = iso of the volume being rendered as an indexed triangle mesh, kept on the
+        device until the next extraction or freeMesh().  Returns (vertices, triangles)."""
+        nv, nt = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.vr_extract_isosurface(self._h, int(iso), C.byref(nv), C.byref(nt)))
+        return int(nv.value), int(nt.value)
+
+    def meshInfo(self):
+        """the resident mesh: dict(iso, vertices, triangles)"""
+        iso, nv, nt = C.c_int32(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.vr_get_mesh_info(self._h, C.byref(iso), C.byref(nv), C.byref(nt)))
+        return dict(iso=int(iso.value), vertices=int(nv.value), triangles=int(nt.value))
+
+    def readMesh(self):
+        """the resident mesh: positions [nv, 3] float32 in the spacing's units, unit normals [nv, 3] float32, triangles [nt, 3] uint32"""
+        info = self.meshInfo()
+        nv, nt = info["vertices"], info["triangles"]
+        pos, nrm = np.zeros((nv, 3), dtype=np.float32), np.zeros((nv, 3), dtype=np.float32)
+        tri = np.zeros((nt, 3), dtype=np.uint32)
+        self._check(self._lib.vr_read_mesh(self._h, _fp(pos), _fp(nrm), tri.ctypes.data_as(C.POINTER(C.c_uint32)), nv, nt))
+        return pos, nrm, tri
+
+    def saveMesh(self, fn, ext):
+        """vr_save_mesh: the resident mesh as binary STL (ext "stl") or binary PLY ("ply")"""
+        self._check(self._lib.vr_save_mesh(self._h, str(fn).encode(), str(ext).encode()))
+
+    def freeMesh(self):
+        self._check(self._lib.vr_free_mesh(self._h))
+
+    def setMeshWorkspace(self, nbytes):
+        self._check(self._lib.vr_set_mesh_workspace(self._h, C.c_uint64(int(nbytes))))
+
+    def meshMs(self) -> float:
+        """HIP-event time of the last extractIsosurface's kernels, ms"""
+        ms = C.c_float(0.0)
+        self._check(self._lib.vr_get_mesh_ms(self._h, C.byref(ms)))
+        return float(ms.value)
 
     def setKernelVariant(self, variant):
         self._check(self._lib.vr_set_kernel_variant(self._h, variant))
