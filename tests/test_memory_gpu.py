@@ -90,3 +90,82 @@ def test_trial_frames_of_the_measured_choice_are_flagged(vra):
         r.setAutotune(False)
         r.render()
         assert not (r.last_launch_choice & 256)
+
+
+def test_per_pixel_targets_are_counted(vra):
+    """vr_get_resident_bytes reports everything resident: the depth target of the isosurface frames and the values target of the
+    reslice frames (one float a pixel each) count under `other`, and stay when their modes are switched off"""
+    R = vra.renderer
+    W, H = 64, 48
+    with vra.RendererCore(0) as r:
+        r.setup((W, H)); assert r.loadShader("VolumeRenderer.cs"); r.setQuirks(0)
+        r.generateSynthetic(R.SYNTH_SPHERE_U8, (32, 32, 32), 1, 14)
+        r.render()
+        other = r.residentBytes()[2]
+        r.setIsosurface(True, 128); r.render()
+        assert r.residentBytes()[2] == other + W * H * 4
+        r.setIsosurface(False)
+        r.setReslice(True, vra.axis_reslice("axial", 16, (32, 32, 32), (1.0, 1.0, 1.0), (W, H))); r.render()
+        assert r.residentBytes()[2] == other + 2 * W * H * 4
+        r.setReslice(False)
+        assert r.residentBytes()[2] == other + 2 * W * H * 4                   # the targets are kept ...
+        r.render()
+        assert r.residentBytes()[2] == other + 2 * W * H * 4                   # ... also over the next composite frame
+
+
+def test_the_accounting_is_stable_over_a_life_cycle(vra, oracle):
+    """one handle through every call that allocates, replaces or frees device memory, twice: the second cycle ends on the resident
+    bytes of the first (nothing leaks, nothing is counted twice) and renders the same frame"""
+    R = vra.renderer
+    N, W, H = 48, 64, 64
+    vol = oracle.gen_noise_ball((N, N, N), 2, 7)
+
+    def copies(r):
+        return r.residentBytes()[1]
+
+    def cycle(r):
+        r.setFilter(R.FILTER_NEAREST); r.resetCamera(); r.setWindow(0, 4095); r.setAlpha(0.05)
+        nearest = frame_of(r)
+        r.setFilter(R.FILTER_TRILINEAR); r.cameraOrient(0.0, 0.66, -1.65)
+        r.render()
+        assert copies(r) > 0 and r.trilinearCopyBytes() > 0
+        r.setIsosurface(True, 1500); r.render(); r.setIsosurface(False)
+        r.setReslice(True, vra.axis_reslice("axial", N // 2, (N, N, N), (1.0, 1.0, 1.0), (W, H))); r.render(); r.setReslice(False)
+        r.setShading(True); r.render(); r.setShading(False)
+        r.countSamples()
+        r.readPixelsRGBA8()
+        r.extractIsosurface(1500); r.freeMesh()
+        assert copies(r) > 0
+        r.smoothVolume((1, 0, 2))
+        assert copies(r) == 0
+        r.render()
+        assert copies(r) > 0
+        r.smoothVolume(0)
+        assert copies(r) == 0
+        r.render()
+        assert copies(r) > 0
+        r.setLayout(R.LAYOUT_LINEAR)
+        assert copies(r) == 0
+        r.render()
+        r.setLayout(R.LAYOUT_BRICKED)
+        assert copies(r) == 0
+        r.render()
+        assert copies(r) > 0
+        r.setCopyBudget(0)
+        assert copies(r) == 0
+        r.render()
+        assert copies(r) == 0
+        r.setCopyBudget(r.COPY_BUDGET_AUTO)
+        r.render()
+        assert copies(r) > 0
+        r.setVolume(vol)
+        assert copies(r) == 0
+        return r.residentBytes(), nearest
+
+    with vra.RendererCore(0) as r:
+        r.setup((W, H)); assert r.loadShader("VolumeRenderer.cs"); r.setQuirks(0)
+        r.setVolume(vol)
+        first, frame1 = cycle(r)
+        second, frame2 = cycle(r)
+        assert second == first
+        assert np.array_equal(frame1.view(np.uint32), frame2.view(np.uint32))

@@ -25,7 +25,6 @@
 namespace vr {
 
 namespace {
-constexpr uint32_t kQuirkTruncGrid = 1u << 0, kQuirkU16Offset = 1u << 1;
 constexpr int kLocalSize = 16;   // layout(local_size_x = 16, local_size_y = 16), VolumeRenderer.cs:3
 }  // namespace
 
@@ -38,10 +37,9 @@ RendererCore::RendererCore(int device) : main_cam(30), histogram(256, 0.0f), dev
         if (device_ >= n) throw NoDeviceError("HIP device ordinal out of range");
         check(hipSetDevice(device_), "hipSetDevice");
         check(hipStreamCreateWithFlags(&own_stream_, hipStreamNonBlocking), "hipStreamCreate");
-        check(hipEventCreate(&ev0_), "hipEventCreate");
-        check(hipEventCreate(&ev1_), "hipEventCreate");
-        for (TuneSlot &s : tune_slot_) { check(hipEventCreate(&s.ev0), "hipEventCreate"); check(hipEventCreate(&s.ev1), "hipEventCreate"); }
-        check(hipMalloc(&d_scratch_, sizeof(unsigned) * 264), "hipMalloc(scratch)");
+        ev0_.create(); ev1_.create();
+        for (TuneSlot &s : tune_slot_) { s.ev0.create(); s.ev1.create(); }
+        d_scratch_.alloc(264, "scratch");
     }
 }
 
@@ -50,37 +48,15 @@ RendererCore::~RendererCore()
     if (device_ >= 0) {
         (void)hipSetDevice(device_);
         (void)hipStreamSynchronize(stream());
-        freeVolume();
-        freeMesh();
-        if (d_fb_) (void)hipFree(d_fb_);
-        if (d_tf_) (void)hipFree(d_tf_);
-        if (d_tile_table_) (void)hipFree(d_tile_table_);
-        if (d_tile_table_tall_) (void)hipFree(d_tile_table_tall_);
-        if (d_tile_table_small_) (void)hipFree(d_tile_table_small_);
-        if (d_tile_work_) (void)hipFree(d_tile_work_);
-        if (d_spp_) (void)hipFree(d_spp_);
-        if (d_depth_) (void)hipFree(d_depth_);
-        if (d_values_) (void)hipFree(d_values_);
-        if (d_scratch_) (void)hipFree(d_scratch_);
-        if (d_rgba8_) (void)hipFree(d_rgba8_);
-        releasePresent();
-        if (ev0_) (void)hipEventDestroy(ev0_);
-        if (ev1_) (void)hipEventDestroy(ev1_);
-        for (TuneSlot &s : tune_slot_) { if (s.ev0) (void)hipEventDestroy(s.ev0); if (s.ev1) (void)hipEventDestroy(s.ev1); }
+        if (present_stream_) { (void)hipStreamSynchronize(present_stream_); (void)hipStreamDestroy(present_stream_); }
         if (own_stream_) (void)hipStreamDestroy(own_stream_);
     }
-}
+}   // (the buffers and events release themselves after this body: nothing is in flight, and releasing them needs no stream)
 
 void RendererCore::requireDevice(const char *what) const
 {
     if (device_ < 0) throw NoDeviceError(std::string(what) + ": host-only handle, no HIP device");
-    hipError_t e = hipSetDevice(device_);
-    if (e != hipSuccess) throw HipError(e, std::string("hipSetDevice: ") + hipGetErrorString(e));
-}
-
-void RendererCore::check(hipError_t e, const char *what) const
-{
-    if (e != hipSuccess) throw HipError(e, std::string(what) + ": " + hipGetErrorString(e));
+    hipCheck(hipSetDevice(device_), "hipSetDevice");
 }
 
 // ---------------------------------------------------------------- setup / FBO / UBO
@@ -95,10 +71,9 @@ void RendererCore::setupFBO()
         throw std::runtime_error("Framebuffer not complete. Error code: zero-sized framebuffer");
     if (device_ < 0) return;   // host-only handle: nothing to allocate
     requireDevice("setupFBO");
-    if (d_fb_) { check(hipFree(d_fb_), "hipFree(fb)"); d_fb_ = nullptr; }
     const size_t n = (size_t)framebuffer_size[0] * (size_t)framebuffer_size[1];
-    check(hipMalloc(reinterpret_cast<void **>(&d_fb_), n * sizeof(float4)), "hipMalloc(framebuffer)");
-    check(hipMemsetAsync(d_fb_, 0, n * sizeof(float4), stream()), "hipMemset(framebuffer)");
+    d_fb_.alloc(n, "framebuffer");
+    check(hipMemsetAsync(d_fb_.get(), 0, n * sizeof(float4), stream()), "hipMemset(framebuffer)");
     check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
 }
 
@@ -210,11 +185,6 @@ void RendererCore::setQuirks(uint32_t q)
 }
 
 // ---------------------------------------------------------------- volume
-// bricks per axis of the VR_LAYOUT_BRICKED storage (vr_frame.h: BRICK_X x BRICK_Y x BRICK_Z voxels)
-static inline uint32_t bricksX(int n) { return (uint32_t)((n + BRICK_X - 1) / BRICK_X); }
-static inline uint32_t bricksY(int n) { return (uint32_t)((n + BRICK_Y - 1) / BRICK_Y); }
-static inline uint32_t bricksZ(int n) { return (uint32_t)((n + BRICK_Z - 1) / BRICK_Z); }
-
 size_t RendererCore::storageVoxels(int nx, int ny, int nz, int lay) const
 {
     if (lay == 0) return (size_t)nx * (size_t)ny * (size_t)nz;
@@ -223,8 +193,7 @@ size_t RendererCore::storageVoxels(int nx, int ny, int nz, int lay) const
 
 void RendererCore::freeVolume()
 {
-    if (d_vol_) { (void)hipFree(d_vol_); d_vol_ = nullptr; vol_alloc_bytes_ = 0; }
-    if (d_loaded_) { (void)hipFree(d_loaded_); d_loaded_ = nullptr; loaded_alloc_bytes_ = 0; }
+    d_vol_.reset(); d_loaded_.reset();
     smooth_sigma_[0] = smooth_sigma_[1] = smooth_sigma_[2] = 0.0f;
     res_dims_[0] = res_dims_[1] = res_dims_[2] = 0; res_bytes_ = 0;
     dropDerived();
@@ -232,27 +201,16 @@ void RendererCore::freeVolume()
 
 void RendererCore::dropDerived()
 {
-    if (d_skip_grid_) { (void)hipFree(d_skip_grid_); d_skip_grid_ = nullptr; skip_grid_cells_ = 0; }
     if (tile_table_skip_sig_ != 0) tile_table_skip_sig_ = -1;            // (an order built on the old volume's visibility)
-    if (d_vol12_) { (void)hipFree(d_vol12_); d_vol12_ = nullptr; vol12_bytes_ = 0; }
-    vol12_failed_ = false;
-    if (d_apron_) { (void)hipFree(d_apron_); d_apron_ = nullptr; apron_bytes_ = 0; }
-    for (void *&q : d_apron_perm_) if (q) { (void)hipFree(q); q = nullptr; }
-    apron_failed_ = false;
-    apron_perm_failed_ = false;
+    copies_.dropAll();
 }
 
-void *RendererCore::allocVolumeBuffer(int nx, int ny, int nz, int bytes, int lay, size_t &alloc_bytes)
+DeviceBuffer<uint8_t> RendererCore::allocVolumeBuffer(int nx, int ny, int nz, int bytes, int lay)
 {
     // + one x/y slab of slack so a one-past-the-edge index can never fault
     const size_t need = (storageVoxels(nx, ny, nz, lay) + (size_t)nx * (size_t)ny + 256) * (size_t)bytes;
-    void *p = nullptr;
-    check(hipMalloc(&p, need), "hipMalloc(volume)");
-    alloc_bytes = need;
-    if (lay != 0) {
-        const hipError_t e = hipMemsetAsync(p, 0, need, stream());
-        if (e != hipSuccess) { (void)hipFree(p); check(e, "hipMemset(volume)"); }
-    }
+    DeviceBuffer<uint8_t> p(need, "volume");
+    if (lay != 0) check(hipMemsetAsync(p.get(), 0, need, stream()), "hipMemset(volume)");
     return p;
 }
 
@@ -260,7 +218,7 @@ void RendererCore::allocVolume(int nx, int ny, int nz, int bytes, int lay)
 {
     requireDevice("volume upload");
     freeVolume();
-    d_vol_ = allocVolumeBuffer(nx, ny, nz, bytes, lay, vol_alloc_bytes_);
+    d_vol_ = allocVolumeBuffer(nx, ny, nz, bytes, lay);
     vol_layout_ = lay;
 }
 
@@ -276,17 +234,15 @@ void RendererCore::setVolume(const void *host, int nx, int ny, int nz, int bytes
     const uint32_t bnx = bricksX(nx), bny = bricksY(ny);
     if (layout == 0) {
         allocVolume(nx, ny, nz, bytes, 0);
-        check(hipMemcpyAsync(d_vol_, host, lin_bytes, hipMemcpyHostToDevice, stream()), "hipMemcpy(volume)");
+        check(hipMemcpyAsync(d_vol_.get(), host, lin_bytes, hipMemcpyHostToDevice, stream()), "hipMemcpy(volume)");
     } else {
-        void *staging = nullptr;
-        check(hipMalloc(&staging, lin_bytes), "hipMalloc(staging)");
-        hipError_t e = hipMemcpyAsync(staging, host, lin_bytes, hipMemcpyHostToDevice, stream());
+        DeviceBuffer<uint8_t> staging(lin_bytes, "staging");
+        hipError_t e = hipMemcpyAsync(staging.get(), host, lin_bytes, hipMemcpyHostToDevice, stream());
         if (e == hipSuccess) {
-            try { allocVolume(nx, ny, nz, bytes, 1); } catch (...) { (void)hipFree(staging); throw; }
-            e = launch_relayout(staging, d_vol_, bytes, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, bnx, bny, 0, stream());
+            allocVolume(nx, ny, nz, bytes, 1);
+            e = launch_relayout(staging.get(), d_vol_.get(), bytes, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, bnx, bny, 0, stream());
         }
         if (e == hipSuccess) e = hipStreamSynchronize(stream());
-        (void)hipFree(staging);
         check(e, "volume relayout");
     }
     check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
@@ -306,7 +262,7 @@ void RendererCore::generateSynthetic(int kind, int nx, int ny, int nz, int bytes
         throw std::invalid_argument("generateSynthetic: volume too large");
     requireDevice("generateSynthetic");
     allocVolume(nx, ny, nz, bytes, layout);
-    check(launch_gen_volume(d_vol_, bytes, kind, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, param, layout,
+    check(launch_gen_volume(d_vol_.get(), bytes, kind, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, param, layout,
                             bricksX(nx), bricksY(ny), stream()),
           "gen_volume_kernel");
     check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
@@ -324,18 +280,16 @@ void RendererCore::readVolume(void *host, size_t bytes)
     const size_t lin_bytes = (size_t)res_dims_[0] * res_dims_[1] * res_dims_[2] * (size_t)res_bytes_;
     if (!host || bytes < lin_bytes) throw std::invalid_argument("readVolume: buffer too small");
     if (vol_layout_ == 0) {
-        check(hipMemcpyAsync(host, d_vol_, lin_bytes, hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H volume)");
+        check(hipMemcpyAsync(host, d_vol_.get(), lin_bytes, hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H volume)");
         check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
         return;
     }
-    void *staging = nullptr;
-    check(hipMalloc(&staging, lin_bytes), "hipMalloc(staging)");
-    hipError_t e = launch_relayout(d_vol_, staging, res_bytes_, (uint32_t)res_dims_[0], (uint32_t)res_dims_[1],
+    DeviceBuffer<uint8_t> staging(lin_bytes, "staging");
+    hipError_t e = launch_relayout(d_vol_.get(), staging.get(), res_bytes_, (uint32_t)res_dims_[0], (uint32_t)res_dims_[1],
                                    (uint32_t)res_dims_[2], bricksX(res_dims_[0]),
                                    bricksY(res_dims_[1]), 1, stream());
-    if (e == hipSuccess) e = hipMemcpyAsync(host, staging, lin_bytes, hipMemcpyDeviceToHost, stream());
+    if (e == hipSuccess) e = hipMemcpyAsync(host, staging.get(), lin_bytes, hipMemcpyDeviceToHost, stream());
     if (e == hipSuccess) e = hipStreamSynchronize(stream());
-    (void)hipFree(staging);
     check(e, "readVolume");
 }
 
@@ -346,369 +300,20 @@ void RendererCore::setLayout(int lay)
     if (!d_vol_ || vol_layout_ == lay) return;
     requireDevice("setLayout");
     const int nx = res_dims_[0], ny = res_dims_[1], nz = res_dims_[2], bytes = res_bytes_;
-    // the rendered volume and, beside a smoothed one, the loaded volume: both into new storage, then swapped in together
-    // (a failure leaves the handle as it was); the smoothing is not computed again
-    void *fresh[2] = {nullptr, nullptr}, *old[2] = {d_vol_, d_loaded_};
-    size_t fresh_bytes[2] = {0, 0};
+    // the rendered volume and, beside a smoothed one, the loaded volume: both into new storage, then moved in together
+    // (a failure leaves the handle as it was: `fresh` frees itself, which waits for the kernels); the smoothing is not computed again
+    DeviceBuffer<uint8_t> fresh[2], *old[2] = {&d_vol_, &d_loaded_};
     hipError_t e = hipSuccess;
-    try {
-        for (int b = 0; b < 2 && e == hipSuccess; b++) {
-            if (!old[b]) continue;
-            fresh[b] = allocVolumeBuffer(nx, ny, nz, bytes, lay, fresh_bytes[b]);
-            e = launch_relayout(old[b], fresh[b], bytes, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, bricksX(nx), bricksY(ny), lay == 0 ? 1 : 0, stream());
-        }
-    } catch (...) {
-        (void)hipStreamSynchronize(stream());
-        for (void *q : fresh) if (q) (void)hipFree(q);
-        throw;
+    for (int b = 0; b < 2 && e == hipSuccess; b++) {
+        if (!*old[b]) continue;
+        fresh[b] = allocVolumeBuffer(nx, ny, nz, bytes, lay);
+        e = launch_relayout(old[b]->get(), fresh[b].get(), bytes, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, bricksX(nx), bricksY(ny), lay == 0 ? 1 : 0, stream());
     }
     const hipError_t es = hipStreamSynchronize(stream());
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) {
-        for (void *q : fresh) if (q) (void)hipFree(q);
-        check(e, "relayout");
-    }
-    for (void *q : old) if (q) (void)hipFree(q);
-    d_vol_ = fresh[0]; vol_alloc_bytes_ = fresh_bytes[0];
-    d_loaded_ = fresh[1]; loaded_alloc_bytes_ = fresh_bytes[1];
+    check(e == hipSuccess ? es : e, "relayout");
+    d_vol_ = std::move(fresh[0]); d_loaded_ = std::move(fresh[1]);
     vol_layout_ = lay;
     dropDerived();
-}
-
-// ---------------------------------------------------------------- smoothing (vr_smooth_volume)
-// The passes of one smoothing, src -> dst (both allocVolume storage in vol_layout_): x, then y, then z, an axis with sigma 0
-// skipped.  With one pass the voxels go straight from src to dst.  With more, fp32 planes carry the intermediates: the whole
-// volume's where one buffer fits the workspace bound, else z slabs -- the passes before z then also cover the r_z planes on
-// either side of the slab, which the z pass reads (every plane of a slab is computed from the same inputs by the same
-// operations as in one piece: the result does not depend on the slab size).  The buffers are freed before this returns.
-void RendererCore::smoothPasses(const void *src, void *dst, const float sigma[3])
-{
-    const int nx = res_dims_[0], ny = res_dims_[1], nz = res_dims_[2];
-    float w[3][2 * kSmoothMaxRadius + 1];
-    int r[3] = {0, 0, 0}, axes[3], n = 0;
-    for (int a = 0; a < 3; a++)
-        if (sigma[a] > 0.0f) {
-            if (!smooth_weights(sigma[a], w[a], 2 * kSmoothMaxRadius + 1, &r[a])) throw std::invalid_argument("smoothVolume: bad sigma");
-            axes[n++] = a;
-        }
-    SmoothPass S = {};
-    S.bytes_per_voxel = res_bytes_; S.layout = vol_layout_;
-    S.nx = nx; S.ny = ny; S.nz = nz;
-    auto pass = [&](int a, const void *in, bool in_float, void *out, bool out_float, int buf_z0, int buf_planes, int z0, int z1) {
-        S.in = in; S.out = out; S.in_float = in_float; S.out_float = out_float;
-        S.in_z0 = S.out_z0 = buf_z0; S.in_planes = S.out_planes = buf_planes;
-        S.axis = a; S.z_begin = z0; S.z_end = z1; S.radius = r[a]; S.weights = w[a];
-        return launch_smooth_pass(S, stream());
-    };
-    // the passes between ev0_ and ev1_ (the events render() times frames with): lastSmoothMs
-    auto finish = [&](hipError_t e) {
-        if (e == hipSuccess) e = hipEventRecord(ev1_, stream());
-        const hipError_t es = hipStreamSynchronize(stream());
-        if (e == hipSuccess) e = es;
-        if (e == hipSuccess) e = hipEventElapsedTime(&last_smooth_ms_, ev0_, ev1_);
-        return e;
-    };
-    last_smooth_ms_ = 0.0f;
-    if (n == 1) {
-        hipError_t e = hipEventRecord(ev0_, stream());
-        if (e == hipSuccess) e = pass(axes[0], src, false, dst, false, 0, 0, 0, nz);
-        check(finish(e), "smooth kernel");
-        return;
-    }
-    const int rz = sigma[2] > 0.0f ? r[2] : 0;           // planes either side of a slab the passes before z must cover
-    const uint64_t plane_bytes = (uint64_t)nx * (uint64_t)ny * sizeof(float);
-    const int nbuf = n - 1;
-    uint64_t bound = smooth_workspace_limit;
-    if (bound == 0) {
-        bound = 2ull << 30;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const uint64_t reserve = std::max<uint64_t>(kCopyReserveBytes, (uint64_t)total_b / 10);   // (what copyFits keeps free)
-            bound = std::min<uint64_t>(bound, (uint64_t)free_b > reserve ? ((uint64_t)free_b - reserve) / (uint64_t)nbuf : 0);
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    uint64_t planes = std::min<uint64_t>(bound / plane_bytes, (uint64_t)nz);
-    if (planes < (uint64_t)std::min(nz, 2 * rz + 1))
-        throw DeviceMemoryError(hipErrorOutOfMemory, "smoothVolume: the workspace cannot hold one slab of fp32 planes");
-    const int slab = planes >= (uint64_t)nz ? nz : (int)planes - 2 * rz;      // output planes per slab
-    void *buf[2] = {nullptr, nullptr};
-    for (int b = 0; b < nbuf; b++)
-        if (hipMalloc(&buf[b], planes * plane_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            if (buf[0]) (void)hipFree(buf[0]);
-            throw DeviceMemoryError(hipErrorOutOfMemory, "smoothVolume: hipMalloc(fp32 planes) failed");
-        }
-    hipError_t e = hipEventRecord(ev0_, stream());
-    for (int s0 = 0; s0 < nz && e == hipSuccess; s0 += slab) {
-        const int s1 = std::min(s0 + slab, nz), e0 = std::max(s0 - rz, 0), e1 = std::min(s1 + rz, nz);
-        const void *in = src;
-        for (int k = 0; k < n && e == hipSuccess; k++) {
-            const bool last = k == n - 1;
-            void *out = last ? dst : buf[k & 1];
-            e = pass(axes[k], in, k > 0, out, !last, e0, e1 - e0, last ? s0 : e0, last ? s1 : e1);
-            in = out;
-        }
-    }
-    e = finish(e);
-    for (void *q : buf) if (q) (void)hipFree(q);
-    check(e, "smooth kernel");
-}
-
-void RendererCore::smoothVolume(float sigma_x, float sigma_y, float sigma_z)
-{
-    const float sigma[3] = {sigma_x, sigma_y, sigma_z};
-    for (float s : sigma)
-        if (!std::isfinite(s) || s < 0.0f || s > kSmoothMaxSigma) throw std::invalid_argument("smoothVolume: every sigma must be finite and in [0, 8] voxels");
-    requireDevice("smoothVolume");
-    if (!d_vol_) throw std::runtime_error("smoothVolume: no dataset loaded");
-    check(hipStreamSynchronize(stream()), "hipStreamSynchronize");      // frames in flight read the buffers replaced below
-    const bool off = sigma_x == 0.0f && sigma_y == 0.0f && sigma_z == 0.0f;
-    if (off && !d_loaded_) return;                                       // rendering the loaded volume already
-    // The volume to render next: the loaded one again, or a new buffer the passes fill.  It is swapped in first and swapped back
-    // if the range scan fails, so a call that throws leaves the handle as it was.
-    void *next = d_loaded_;
-    size_t next_bytes = loaded_alloc_bytes_;
-    if (!off) {
-        try {
-            next = allocVolumeBuffer(res_dims_[0], res_dims_[1], res_dims_[2], res_bytes_, vol_layout_, next_bytes);
-        } catch (const HipError &err) {
-            (void)hipGetLastError();
-            throw DeviceMemoryError(err.code, std::string("smoothVolume: ") + err.what());
-        }
-        try { smoothPasses(d_loaded_ ? d_loaded_ : d_vol_, next, sigma); } catch (...) { (void)hipStreamSynchronize(stream()); (void)hipFree(next); throw; }
-    }
-    void *const old_vol = d_vol_;
-    const size_t old_bytes = vol_alloc_bytes_;
-    const int keep[8] = {min_val, max_val, min_dataset_val, max_dataset_val, exact_min_, exact_max_, 0, 0};
-    d_vol_ = next; vol_alloc_bytes_ = next_bytes;
-    try {
-        scanDatasetRange();                                              // the ranges of the rendered volume; it also sets the window from the data ...
-    } catch (...) {
-        (void)hipStreamSynchronize(stream());
-        d_vol_ = old_vol; vol_alloc_bytes_ = old_bytes;
-        min_val = keep[0]; max_val = keep[1]; min_dataset_val = keep[2]; max_dataset_val = keep[3]; exact_min_ = keep[4]; exact_max_ = keep[5];
-        if (!off) (void)hipFree(next);
-        throw;
-    }
-    min_val = keep[0]; max_val = keep[1];                                // ... which is the user's and stays; no message, camera and uniforms untouched
-    if (off) {
-        (void)hipFree(old_vol);                                          // the smoothed volume
-        d_loaded_ = nullptr; loaded_alloc_bytes_ = 0;
-    } else if (d_loaded_) {
-        (void)hipFree(old_vol);                                          // the earlier smoothing result
-    } else {
-        d_loaded_ = old_vol; loaded_alloc_bytes_ = old_bytes;
-    }
-    for (int a = 0; a < 3; a++) smooth_sigma_[a] = sigma[a];
-    dropDerived();                                                       // what a load leaves behind for new voxels
-}
-
-// ---------------------------------------------------------------- extraction (vr_extract_isosurface)
-uint64_t RendererCore::meshBytes() const { return mesh_nv_ * 24 + mesh_nt_ * 12; }
-
-void RendererCore::freeMesh()
-{
-    if (d_mesh_pos_) (void)hipFree(d_mesh_pos_);
-    if (d_mesh_nrm_) (void)hipFree(d_mesh_nrm_);
-    if (d_mesh_tri_) (void)hipFree(d_mesh_tri_);
-    d_mesh_pos_ = d_mesh_nrm_ = nullptr; d_mesh_tri_ = nullptr;
-    mesh_nv_ = mesh_nt_ = 0;
-    mesh_valid_ = false;
-}
-
-// Two passes over the z slabs the workspace allows.  The first counts and scans every slab and keeps only the slabs' totals: the
-// mesh's size is known, and checked, before anything of it is allocated.  The second counts and scans a slab again (not where one
-// slab is the whole volume: its arrays are still there) and emits its vertices and triangles at the bases the totals give; a slab
-// without a vertex is skipped.  The arrays are freed before this returns; the previous mesh is replaced only at the very end.
-void RendererCore::extractIsosurface(int32_t iso, uint64_t *n_vertices, uint64_t *n_triangles)
-{
-    requireDevice("extractIsosurface");
-    if (!d_vol_) throw std::runtime_error("extractIsosurface: no dataset loaded");
-    const int nx = res_dims_[0], ny = res_dims_[1], nz = res_dims_[2];
-    struct Scratch {                                     // device allocations of this call; hipFree waits for the kernels that use them
-        std::vector<void *> p;
-        ~Scratch() { for (void *q : p) if (q) (void)hipFree(q); }
-        void *get(size_t bytes, const char *what)
-        {
-            void *q = nullptr;
-            if (hipMalloc(&q, bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                throw DeviceMemoryError(hipErrorOutOfMemory, std::string("extractIsosurface: hipMalloc(") + what + ") failed");
-            }
-            p.push_back(q);
-            return q;
-        }
-        void *release(void *q) { for (void *&r : p) if (r == q) r = nullptr; return q; }
-    } scratch;
-    uint64_t nv = 0, nt = 0;
-    float *pos = nullptr, *nrm = nullptr;
-    uint32_t *tri = nullptr;
-    float ms = 0.0f;
-    if (nx >= 2 && ny >= 2 && nz >= 2) {
-        const uint64_t plane = (uint64_t)nx * (uint64_t)ny;
-        uint64_t bound = mesh_workspace_limit;
-        if (bound == 0) {
-            bound = 2ull << 30;
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                const uint64_t reserve = std::max<uint64_t>(kCopyReserveBytes, (uint64_t)total_b / 10);   // (what copyFits keeps free)
-                bound = std::min<uint64_t>(bound, (uint64_t)free_b > reserve ? (uint64_t)free_b - reserve : 0);
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-        // planes the arrays hold: a slab's own ones and the plane after them
-        uint64_t planes = std::min<uint64_t>(std::min<uint64_t>(bound / (kMeshBytesPerVoxel * plane), kMeshMaxSlabVoxels / plane), (uint64_t)nz);
-        if (planes < 2) throw DeviceMemoryError(hipErrorOutOfMemory, "extractIsosurface: the workspace cannot hold two planes of per-voxel counts");
-        const int slab = planes >= (uint64_t)nz ? nz : (int)planes - 1;
-        const int nslabs = (nz + slab - 1) / slab;
-        const uint64_t words = planes * plane + 1;
-        const size_t temp_bytes = mesh_scan_temp_bytes(words);
-        uint64_t *d_scan = static_cast<uint64_t *>(scratch.get(words * sizeof(uint64_t), "offsets"));
-        uint8_t *d_mask = static_cast<uint8_t *>(scratch.get(planes * plane, "masks"));
-        void *d_temp = scratch.get(temp_bytes ? temp_bytes : 16, "scan scratch");
-        uint64_t *d_totals = static_cast<uint64_t *>(scratch.get((size_t)nslabs * 2 * sizeof(uint64_t), "totals"));
-        MeshSlab S = {};
-        S.volume = d_vol_; S.bytes_per_voxel = res_bytes_; S.layout = vol_layout_;
-        S.nx = nx; S.ny = ny; S.nz = nz;
-        S.iso_s = (float)((int64_t)iso + (datasize_bytes == 2 && (quirks & kQuirkU16Offset) ? 1000 : 0));   // isoStored's rule
-        for (int a = 0; a < 3; a++) S.spacing[a] = voxel_size[a];
-        S.scan = d_scan; S.mask = d_mask;
-        auto countAndScan = [&](int s) {
-            S.z0 = s * slab; S.z1 = std::min(S.z0 + slab, nz);
-            hipError_t e = launch_mesh_count(S, stream());
-            if (e == hipSuccess) e = launch_mesh_scan(d_scan, mesh_scan_words(S), d_temp, temp_bytes, stream());
-            return e;
-        };
-        auto timed = [&](hipError_t e) {                 // the kernels between ev0_ and ev1_ (the events render() times frames with)
-            if (e == hipSuccess) e = hipEventRecord(ev1_, stream());
-            const hipError_t es = hipStreamSynchronize(stream());
-            if (e == hipSuccess) e = es;
-            float t = 0.0f;
-            if (e == hipSuccess) e = hipEventElapsedTime(&t, ev0_, ev1_);
-            ms += t;
-            return e;
-        };
-        hipError_t e = hipEventRecord(ev0_, stream());
-        for (int s = 0; s < nslabs && e == hipSuccess; s++) {
-            e = countAndScan(s);
-            // vertices of the slab's own planes: the offset of the first voxel after them; triangles: the last word's offset
-            if (e == hipSuccess) e = hipMemcpyAsync(d_totals + 2 * s, d_scan + (uint64_t)(S.z1 - S.z0) * plane, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream());
-            if (e == hipSuccess) e = hipMemcpyAsync(d_totals + 2 * s + 1, d_scan + mesh_scan_words(S) - 1, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream());
-        }
-        check(timed(e), "extraction kernels (count)");
-        std::vector<uint64_t> totals((size_t)nslabs * 2);
-        check(hipMemcpy(totals.data(), d_totals, totals.size() * sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy(D2H totals)");
-        std::vector<uint64_t> vbase((size_t)nslabs), tbase((size_t)nslabs);
-        for (int s = 0; s < nslabs; s++) {
-            vbase[s] = nv; tbase[s] = nt;
-            nv += totals[2 * s] & 0xffffffffull;
-            nt += totals[2 * s + 1] >> 32;
-        }
-        if (nv > 0xffffffffull || nt > 0xffffffffull) {
-            setMessage("Error!", "The isosurface has " + std::to_string(nv) + " vertices and " + std::to_string(nt) +
-                                     " triangles: more than 32-bit indices address. Smooth the volume or choose another iso value.");
-            throw std::invalid_argument("extractIsosurface: more than 2^32 - 1 vertices or triangles");
-        }
-        if (nv > 0) {
-            pos = static_cast<float *>(scratch.get(nv * 12, "positions"));
-            nrm = static_cast<float *>(scratch.get(nv * 12, "normals"));
-        }
-        if (nt > 0) tri = static_cast<uint32_t *>(scratch.get(nt * 12, "triangles"));
-        if (nv > 0) {
-            S.positions = pos; S.normals = nrm; S.triangles = tri;
-            e = hipEventRecord(ev0_, stream());
-            for (int s = 0; s < nslabs && e == hipSuccess; s++) {
-                if ((totals[2 * s] & 0xffffffffull) == 0) continue;
-                if (nslabs > 1) e = countAndScan(s);
-                else { S.z0 = 0; S.z1 = nz; }
-                S.vertex_base = vbase[s]; S.triangle_base = tbase[s];
-                if (e == hipSuccess) e = launch_mesh_emit(S, stream());
-            }
-            check(timed(e), "extraction kernels (emit)");
-        }
-    }
-    freeMesh();
-    d_mesh_pos_ = static_cast<float *>(scratch.release(pos));
-    d_mesh_nrm_ = static_cast<float *>(scratch.release(nrm));
-    d_mesh_tri_ = static_cast<uint32_t *>(scratch.release(tri));
-    mesh_nv_ = nv; mesh_nt_ = nt; mesh_iso_ = iso; mesh_valid_ = true;
-    last_mesh_ms_ = ms;
-    if (n_vertices) *n_vertices = nv;
-    if (n_triangles) *n_triangles = nt;
-}
-
-void RendererCore::meshInfo(int32_t *iso, uint64_t *n_vertices, uint64_t *n_triangles) const
-{
-    if (!mesh_valid_) throw std::invalid_argument("meshInfo: no isosurface has been extracted");
-    if (iso) *iso = mesh_iso_;
-    if (n_vertices) *n_vertices = mesh_nv_;
-    if (n_triangles) *n_triangles = mesh_nt_;
-}
-
-void RendererCore::readMesh(float *positions, float *normals, uint32_t *triangles, uint64_t vertex_capacity, uint64_t triangle_capacity)
-{
-    if (!mesh_valid_) throw std::invalid_argument("readMesh: no isosurface has been extracted");
-    if (((positions || normals) && vertex_capacity < mesh_nv_) || (triangles && triangle_capacity < mesh_nt_))
-        throw std::invalid_argument("readMesh: buffer too small");
-    requireDevice("readMesh");
-    if (positions && mesh_nv_) check(hipMemcpyAsync(positions, d_mesh_pos_, mesh_nv_ * 12, hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H positions)");
-    if (normals && mesh_nv_) check(hipMemcpyAsync(normals, d_mesh_nrm_, mesh_nv_ * 12, hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H normals)");
-    if (triangles && mesh_nt_) check(hipMemcpyAsync(triangles, d_mesh_tri_, mesh_nt_ * 12, hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H triangles)");
-    check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
-}
-
-// "stl": binary STL, the facet normal the unit cross product of the stored positions in double, (0, 0, 0) for a zero-area
-// triangle, attribute word 0.  "ply": binary_little_endian 1.0, x y z nx ny nz as float, faces uchar uint.
-void RendererCore::saveMesh(const std::string &fn, const std::string &ext)
-{
-    if (!mesh_valid_) throw std::invalid_argument("saveMesh: no isosurface has been extracted");
-    if (ext != "stl" && ext != "ply") throw std::invalid_argument("saveMesh: the extension must be \"stl\" or \"ply\"");
-    std::vector<float> pos((size_t)mesh_nv_ * 3), nrm((size_t)mesh_nv_ * 3);
-    std::vector<uint32_t> tri((size_t)mesh_nt_ * 3);
-    readMesh(pos.data(), ext == "ply" ? nrm.data() : nullptr, tri.data(), mesh_nv_, mesh_nt_);
-    FILE *f = std::fopen(fn.c_str(), "wb");
-    if (!f) throw IoError("saveMesh: cannot open " + fn);
-    bool ok = true;
-    auto put = [&](const void *p, size_t n) { ok = ok && (n == 0 || std::fwrite(p, 1, n, f) == n); };
-    if (ext == "stl") {
-        char header[80] = "binary STL written by vr_save_mesh";
-        const uint32_t count = (uint32_t)mesh_nt_;
-        put(header, sizeof(header));
-        put(&count, 4);
-        for (uint64_t t = 0; t < mesh_nt_ && ok; t++) {
-            const float *p0 = &pos[3 * (size_t)tri[3 * t]], *p1 = &pos[3 * (size_t)tri[3 * t + 1]], *p2 = &pos[3 * (size_t)tri[3 * t + 2]];
-            const double u[3] = {(double)p1[0] - p0[0], (double)p1[1] - p0[1], (double)p1[2] - p0[2]};
-            const double v[3] = {(double)p2[0] - p0[0], (double)p2[1] - p0[1], (double)p2[2] - p0[2]};
-            const double c[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
-            const double len = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
-            float rec[12] = {};
-            if (len > 0.0) for (int a = 0; a < 3; a++) rec[a] = (float)(c[a] / len);
-            for (int a = 0; a < 3; a++) { rec[3 + a] = p0[a]; rec[6 + a] = p1[a]; rec[9 + a] = p2[a]; }
-            const uint16_t attribute = 0;
-            put(rec, sizeof(rec));
-            put(&attribute, 2);
-        }
-    } else {
-        const std::string header = "ply\nformat binary_little_endian 1.0\ncomment isosurface at " + std::to_string(mesh_iso_) +
-                                   ", written by vr_save_mesh\nelement vertex " + std::to_string(mesh_nv_) +
-                                   "\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n"
-                                   "element face " + std::to_string(mesh_nt_) + "\nproperty list uchar uint vertex_indices\nend_header\n";
-        put(header.data(), header.size());
-        for (uint64_t v = 0; v < mesh_nv_ && ok; v++) {
-            put(&pos[3 * (size_t)v], 12);
-            put(&nrm[3 * (size_t)v], 12);
-        }
-        const uint8_t three = 3;
-        for (uint64_t t = 0; t < mesh_nt_ && ok; t++) {
-            put(&three, 1);
-            put(&tri[3 * (size_t)t], 12);
-        }
-    }
-    if (std::fclose(f) != 0) ok = false;
-    if (!ok) throw IoError("saveMesh: writing " + fn + " failed");
 }
 
 // min/max scan of src/RendererCore.cpp:360-384 as a device reduction
@@ -716,13 +321,13 @@ void RendererCore::scanDatasetRange()
 {
     // scratch: [0..1] reference-style min/max (index 8390640 skipped), [2..3] exact min/max
     const unsigned init[4] = {0xffffffffu, 0u, 0xffffffffu, 0u};
-    check(hipMemcpyAsync(d_scratch_, init, sizeof(init), hipMemcpyHostToDevice, stream()), "hipMemcpy(scratch)");
-    check(launch_stats(d_vol_, res_bytes_, (uint32_t)res_dims_[0], (uint32_t)res_dims_[1], (uint32_t)res_dims_[2],
+    check(hipMemcpyAsync(d_scratch_.get(), init, sizeof(init), hipMemcpyHostToDevice, stream()), "hipMemcpy(scratch)");
+    check(launch_stats(d_vol_.get(), res_bytes_, (uint32_t)res_dims_[0], (uint32_t)res_dims_[1], (uint32_t)res_dims_[2],
                        vol_layout_, bricksX(res_dims_[0]), bricksY(res_dims_[1]), 0, 1.0f,
-                       d_scratch_, d_scratch_ + 4, stream()),
+                       d_scratch_.get(), d_scratch_.get() + 4, stream()),
           "stats_kernel");
     unsigned mm[4];
-    check(hipMemcpyAsync(mm, d_scratch_, sizeof(mm), hipMemcpyDeviceToHost, stream()), "hipMemcpy(scratch)");
+    check(hipMemcpyAsync(mm, d_scratch_.get(), sizeof(mm), hipMemcpyDeviceToHost, stream()), "hipMemcpy(scratch)");
     check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
     exact_min_ = (int)mm[2];
     exact_max_ = (int)mm[3];
@@ -742,13 +347,13 @@ void RendererCore::computeHistogram(float out[256])
 {
     requireDevice("histogram");
     if (!d_vol_) throw std::runtime_error("histogram: no dataset loaded");
-    check(hipMemsetAsync(d_scratch_, 0, sizeof(unsigned) * 264, stream()), "hipMemset(scratch)");
-    check(launch_stats(d_vol_, res_bytes_, (uint32_t)res_dims_[0], (uint32_t)res_dims_[1], (uint32_t)res_dims_[2],
+    check(hipMemsetAsync(d_scratch_.get(), 0, sizeof(unsigned) * 264, stream()), "hipMemset(scratch)");
+    check(launch_stats(d_vol_.get(), res_bytes_, (uint32_t)res_dims_[0], (uint32_t)res_dims_[1], (uint32_t)res_dims_[2],
                        vol_layout_, bricksX(res_dims_[0]), bricksY(res_dims_[1]), 1,
-                       (float)max_dataset_val, d_scratch_, d_scratch_ + 4, stream()),
+                       (float)max_dataset_val, d_scratch_.get(), d_scratch_.get() + 4, stream()),
           "stats_kernel");
     unsigned counts[256];
-    check(hipMemcpyAsync(counts, d_scratch_ + 4, sizeof(counts), hipMemcpyDeviceToHost, stream()), "hipMemcpy(hist)");
+    check(hipMemcpyAsync(counts, d_scratch_.get() + 4, sizeof(counts), hipMemcpyDeviceToHost, stream()), "hipMemcpy(hist)");
     check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
     // src/RendererCore.cpp:361,400-405: the normaliser starts from the dataset max
     // (16-bit) or -1 (8-bit) and is raised to the largest bin count
@@ -780,21 +385,18 @@ double RendererCore::measureStreamRead(int reps)
     requireDevice("measureStreamRead");
     if (!d_vol_) throw std::runtime_error("measureStreamRead: no dataset loaded");
     const uint64_t bytes = (uint64_t)storageVoxels(res_dims_[0], res_dims_[1], res_dims_[2], vol_layout_) * (uint64_t)res_bytes_ & ~15ull;
-    hipEvent_t a = nullptr, b = nullptr;
-    check(hipEventCreate(&a), "hipEventCreate");
-    check(hipEventCreate(&b), "hipEventCreate");
+    Event a, b; a.create(); b.create();
     double best_ms = 1e30;
-    hipError_t e = hipMemsetAsync(d_scratch_, 0, sizeof(unsigned), stream());
+    hipError_t e = hipMemsetAsync(d_scratch_.get(), 0, sizeof(unsigned), stream());
     for (int r = 0; r < std::max(reps, 1) + 1 && e == hipSuccess; r++) {      // first pass warms up
         e = hipEventRecord(a, stream());
-        if (e == hipSuccess) e = launch_stream_read(d_vol_, bytes, d_scratch_, stream());
+        if (e == hipSuccess) e = launch_stream_read(d_vol_.get(), bytes, d_scratch_.get(), stream());
         if (e == hipSuccess) e = hipEventRecord(b, stream());
         if (e == hipSuccess) e = hipEventSynchronize(b);
         float ms = 0.0f;
         if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
         if (r > 0 && (double)ms < best_ms) best_ms = (double)ms;
     }
-    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
     check(e, "stream_read_kernel");
     return (double)bytes / (best_ms * 1e-3) / 1e9;
 }
@@ -893,8 +495,8 @@ void RendererCore::setTransferFunction(const int32_t *iso, const float *rgba4, i
         tf_grey_ = std::memcmp(&tf_lut_[4 * e], &tf_lut_[4 * e + 1], sizeof(float)) == 0 && std::memcmp(&tf_lut_[4 * e], &tf_lut_[4 * e + 2], sizeof(float)) == 0;
     if (device_ >= 0) {
         requireDevice("setTransferFunction");
-        if (!d_tf_) check(hipMalloc(reinterpret_cast<void **>(&d_tf_), 256 * sizeof(float4)), "hipMalloc(tf)");
-        check(hipMemcpyAsync(d_tf_, tf_lut_.data(), 256 * sizeof(float4), hipMemcpyHostToDevice, stream()), "hipMemcpy(tf)");
+        d_tf_.ensure(256, "tf");
+        check(hipMemcpyAsync(d_tf_.get(), tf_lut_.data(), 256 * sizeof(float4), hipMemcpyHostToDevice, stream()), "hipMemcpy(tf)");
         check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
     }
 }
@@ -937,10 +539,10 @@ bool RendererCore::certifyDivisor(float b)
     bool ok = false;
     if (std::isfinite(b) && b > 1e-30f && b < 1e30f) {
         const float r = 1.0f / b;
-        check(hipMemsetAsync(d_scratch_, 0, sizeof(unsigned), stream()), "hipMemset(scratch)");
-        check(launch_certify_div(b, r, d_scratch_, stream()), "certify_div_kernel");
+        check(hipMemsetAsync(d_scratch_.get(), 0, sizeof(unsigned), stream()), "hipMemset(scratch)");
+        check(launch_certify_div(b, r, d_scratch_.get(), stream()), "certify_div_kernel");
         unsigned bad = 1;
-        check(hipMemcpyAsync(&bad, d_scratch_, sizeof(unsigned), hipMemcpyDeviceToHost, stream()), "hipMemcpy(scratch)");
+        check(hipMemcpyAsync(&bad, d_scratch_.get(), sizeof(unsigned), hipMemcpyDeviceToHost, stream()), "hipMemcpy(scratch)");
         check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
         ok = (bad == 0);
     }
@@ -1077,16 +679,12 @@ void RendererCore::setSkipCells(FrameParams &P) const
 
 // a per-pixel float target beside the colour one (depth, values): grown to this frame's rows x width; a new allocation is filled
 // with the bit pattern `fill` (pixels no later frame writes read as "nothing here")
-void RendererCore::growFloatTarget(float *&d, size_t &capacity, int fill, const char *name)
+void RendererCore::growFloatTarget(DeviceBuffer<float> &d, int fill, const char *name)
 {
     const int rows = std::max(localRows(), framebuffer_size[1]);
     const size_t n = (size_t)rows * (size_t)framebuffer_size[0];
-    if (capacity >= n) return;
-    const std::string of = std::string("(") + name + ")";
-    if (d) { check(hipFree(d), ("hipFree" + of).c_str()); d = nullptr; capacity = 0; }
-    check(hipMalloc(reinterpret_cast<void **>(&d), std::max<size_t>(n, 1) * sizeof(float)), ("hipMalloc" + of).c_str());
-    capacity = n;
-    check(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d), fill, n, stream()), ("hipMemset" + of).c_str());
+    if (!d.ensure(std::max<size_t>(n, 1), name)) return;
+    check(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d.get()), fill, n, stream()), (std::string("hipMemset(") + name + ")").c_str());
 }
 
 float4 *RendererCore::prepareLaunch(FrameParams &P, LaunchConfig &L)
@@ -1095,7 +693,7 @@ float4 *RendererCore::prepareLaunch(FrameParams &P, LaunchConfig &L)
     requireDevice("render");
     if (!cs_program_) throw std::runtime_error("render: no shader loaded (call loadShader first)");
     if (!d_vol_) throw std::runtime_error("render: no dataset loaded");
-    float4 *fb = ext_fb_ ? reinterpret_cast<float4 *>(ext_fb_) : d_fb_;
+    float4 *fb = ext_fb_ ? reinterpret_cast<float4 *>(ext_fb_) : d_fb_.get();
     if (!fb) throw std::runtime_error("render: setup() has not allocated the framebuffer");
     if (fb_format_ == 1 && ext_fb_ && !tf_lut_.empty())
         throw std::invalid_argument("render: the (grey, alpha) target format needs a grey mode (no transfer function)");
@@ -1106,11 +704,11 @@ float4 *RendererCore::prepareLaunch(FrameParams &P, LaunchConfig &L)
         buildFrame(P, L);
         P.skip_empty = 0;
         iso_skip_grid_ = nullptr;
-        if (skip_empty && ensureSkipGrid() && (float)skip_grid_min_ < isoStored()) {
+        if (skip_empty && ensureSkipGrid() && (float)copies_.skipGridMin() < isoStored()) {
             setSkipCells(P);
-            iso_skip_grid_ = d_skip_grid_;
+            iso_skip_grid_ = copies_.skipGrid();
         }
-        growFloatTarget(d_depth_, depth_capacity_, 0x7f800000, "depth");   // +inf
+        growFloatTarget(d_depth_, 0x7f800000, "depth");   // +inf
         depth_rows_ = (ext_fb_ && fb_compact_) ? localRows() : framebuffer_size[1];
         depth_w_ = framebuffer_size[0];
         noMeasuredChoice();
@@ -1121,7 +719,7 @@ float4 *RendererCore::prepareLaunch(FrameParams &P, LaunchConfig &L)
         // table, speed copies or skip grid
         buildFrame(P, L);
         P.skip_empty = 0;
-        growFloatTarget(d_values_, values_capacity_, 0x7fc00000, "values");   // quiet NaN
+        growFloatTarget(d_values_, 0x7fc00000, "values");   // quiet NaN
         values_rows_ = (ext_fb_ && fb_compact_) ? localRows() : framebuffer_size[1];
         values_w_ = framebuffer_size[0];
         noMeasuredChoice();
@@ -1135,9 +733,9 @@ float4 *RendererCore::prepareLaunch(FrameParams &P, LaunchConfig &L)
         P.skip_empty = 0;
         shade_skip_grid_ = nullptr;
         int thresh = 0;
-        if (skip_empty && zeroAlphaThreshold(P, filter == 1, thresh) && ensureSkipGrid() && thresh >= (int)skip_grid_min_) {
+        if (skip_empty && zeroAlphaThreshold(P, filter == 1, thresh) && ensureSkipGrid() && thresh >= (int)copies_.skipGridMin()) {
             setSkipCells(P);
-            shade_skip_grid_ = d_skip_grid_;
+            shade_skip_grid_ = copies_.skipGrid();
             shade_skip_thresh_ = thresh;
         }
         noMeasuredChoice();
@@ -1317,25 +915,10 @@ void RendererCore::refreshPacked12(FrameParams &P, LaunchConfig &L)
     const size_t voxels = storageVoxels(res_dims_[0], res_dims_[1], res_dims_[2], 1);
     const size_t bytes = voxels / 2 * 3;
     if (bytes + 16 >= (1ull << 32)) return;
-    if (!d_vol12_) {
-        if (vol12_failed_) return;
-        if (!copyFits(bytes + 16)) { vol12_failed_ = true; return; }      // (not asked again every frame; vr_set_copy_budget / the next volume re-arm it)
-        if (hipMalloc(&d_vol12_, bytes + 16) != hipSuccess) {     // an optimisation only: render from the volume as loaded
-            (void)hipGetLastError();
-            d_vol12_ = nullptr;
-            vol12_failed_ = true;
-            return;
-        }
-        hipError_t e = launch_pack12(d_vol_, d_vol12_, voxels, (uint32_t)exact_min_, stream());
-        vol12_base_ = exact_min_;
-        if (e == hipSuccess) e = hipStreamSynchronize(stream());
-        if (e != hipSuccess) { (void)hipFree(d_vol12_); d_vol12_ = nullptr; }
-        check(e, "pack12_kernel");
-        vol12_bytes_ = bytes;
-    }
-    L.packed12 = d_vol12_;
-    L.packed12_bytes = (uint32_t)vol12_bytes_;
-    P.pk12_base = vol12_base_;
+    if (!copies_.ensurePacked12(residentVolume(), voxels, bytes)) return;   // (a refusal is not asked again every frame; vr_set_copy_budget / the next volume re-arm it)
+    L.packed12 = copies_.packed12();
+    L.packed12_bytes = (uint32_t)copies_.packed12Bytes();
+    P.pk12_base = copies_.packed12Base();
 }
 
 // TRILINEAR's apron copy (vr_set_trilinear_copy, default on; vr_device.h: build_axis_tables_apron): the bricked
@@ -1348,29 +931,13 @@ void RendererCore::refreshApron(const FrameParams &P, LaunchConfig &L)
     L.apron_y = L.apron_x = nullptr;
     L.apron_bytes = 0;
     last_apron_bytes_ = 0;
-    if (!tri_apron || apron_failed_ || vol_layout_ != 1 || !(tri_path_candidate(P, L) || tri_slab_candidate(P, L))) return;
+    if (!tri_apron || vol_layout_ != 1 || !(tri_path_candidate(P, L) || tri_slab_candidate(P, L))) return;
     const uint64_t bytes = apron_voxels(res_dims_[0], res_dims_[1], res_dims_[2]) * (uint64_t)res_bytes_;
     if (bytes + 16 >= (1ull << 32) && !tri_slab_candidate(P, L)) return;   // the batched kernel gathers through a 32-bit buffer descriptor
-    if (!d_apron_) {
-        if (!copyFits(bytes + 16)) { apron_failed_ = true; return; }   // over the budget / too little device memory left: not an error, and not asked again every frame
-        if (hipMalloc(&d_apron_, bytes + 16) != hipSuccess) {         // an optimisation only
-            (void)hipGetLastError();
-            d_apron_ = nullptr;
-            apron_failed_ = true;
-            return;
-        }
-        hipError_t e = hipMemsetAsync(static_cast<char *>(d_apron_) + bytes, 0, 16, stream());
-        if (e == hipSuccess)
-            e = launch_relayout_apron(d_vol_, d_apron_, res_bytes_, (uint32_t)res_dims_[0], (uint32_t)res_dims_[1], (uint32_t)res_dims_[2],
-                                      vol_layout_, (uint32_t)bricksX(res_dims_[0]), (uint32_t)bricksY(res_dims_[1]), 0, stream());
-        if (e == hipSuccess) e = hipStreamSynchronize(stream());
-        if (e != hipSuccess) { (void)hipFree(d_apron_); d_apron_ = nullptr; }
-        check(e, "relayout_apron_kernel");
-        apron_bytes_ = (size_t)bytes;
-    }
-    L.apron = d_apron_;
-    L.apron_bytes = (uint64_t)apron_bytes_;
-    last_apron_bytes_ = apron_bytes_;
+    if (!copies_.ensureApron(residentVolume(), bytes)) return;          // an optimisation only
+    L.apron = copies_.apron();
+    L.apron_bytes = (uint64_t)copies_.apronBytes();
+    last_apron_bytes_ = copies_.apronBytes();
     // Half layers of the staged kernel (vr_tslab.hip, 16-bit volumes): two more copies with the bricks' planes along y / x
     // slowest, so that half a brick along any major axis is 80 contiguous bytes.  Built the first time a view is oblique
     // to the volume axes (or kernel variants 8 / 9 ask for them); +2 x 1.25 volumes of HBM.
@@ -1381,72 +948,29 @@ void RendererCore::refreshApron(const FrameParams &P, LaunchConfig &L)
     const bool half_layers_possible = (force_generic >= 8 && force_generic <= 9) || (force_generic == 11 && oblique) ||
                                       (force_generic == 0 && oblique && (L.tri_slab >= 3 || autotune));
     const bool want_perm = res_bytes_ == 2 && tri_slab_candidate(P, L) && L.tile_table != nullptr && half_layers_possible;
-    if (want_perm && !apron_perm_failed_ && !(d_apron_perm_[0] && d_apron_perm_[1])) {
-        if (!copyFits(2 * (bytes + 16))) apron_perm_failed_ = true;     // (re-armed by vr_set_copy_budget and by the next volume)
-        for (int o = 0; o < 2 && !apron_perm_failed_; o++) {
-            if (d_apron_perm_[o]) continue;
-            if (hipMalloc(&d_apron_perm_[o], bytes + 16) != hipSuccess) {
-                (void)hipGetLastError();
-                d_apron_perm_[o] = nullptr;
-                apron_perm_failed_ = true;
-                break;
-            }
-            hipError_t e = hipMemsetAsync(static_cast<char *>(d_apron_perm_[o]) + bytes, 0, 16, stream());
-            if (e == hipSuccess)
-                e = launch_relayout_apron(d_vol_, d_apron_perm_[o], res_bytes_, (uint32_t)res_dims_[0], (uint32_t)res_dims_[1], (uint32_t)res_dims_[2],
-                                          vol_layout_, (uint32_t)bricksX(res_dims_[0]), (uint32_t)bricksY(res_dims_[1]), o + 1, stream());
-            if (e == hipSuccess) e = hipStreamSynchronize(stream());
-            if (e != hipSuccess) { (void)hipFree(d_apron_perm_[o]); d_apron_perm_[o] = nullptr; }
-            check(e, "relayout_apron_kernel");
-        }
-        if (apron_perm_failed_)                                         // one without the other is 1.25 volumes of dead memory, in the low-memory case
-            for (void *&q : d_apron_perm_) if (q) { (void)hipFree(q); q = nullptr; }
+    if (want_perm) (void)copies_.ensureApronPerm(residentVolume(), bytes);   // (a refusal is re-armed by vr_set_copy_budget and by the next volume)
+    if (copies_.hasApronPerm()) {
+        L.apron_y = copies_.apronPerm(0);
+        L.apron_x = copies_.apronPerm(1);
+        last_apron_bytes_ += 2 * copies_.apronBytes();
     }
-    if (d_apron_perm_[0] && d_apron_perm_[1]) {
-        L.apron_y = d_apron_perm_[0];
-        L.apron_x = d_apron_perm_[1];
-        last_apron_bytes_ += 2 * apron_bytes_;
-    }
-}
-
-uint64_t RendererCore::copiesBytes() const
-{
-    uint64_t b = d_vol12_ ? (uint64_t)vol12_bytes_ + 16 : 0;
-    if (d_apron_) b += (uint64_t)apron_bytes_ + 16;
-    for (void *q : d_apron_perm_) if (q) b += (uint64_t)apron_bytes_ + 16;
-    return b;
-}
-
-bool RendererCore::copyFits(uint64_t bytes) const
-{
-    if (copy_budget_ != kCopyBudgetAuto) return copiesBytes() + bytes <= copy_budget_;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return true; }
-    const uint64_t reserve = std::max<uint64_t>(kCopyReserveBytes, (uint64_t)total_b / 10);
-    return (uint64_t)free_b >= bytes + reserve;       // mandatory allocations (skip grid, targets, group slots) keep room
 }
 
 void RendererCore::setCopyBudget(uint64_t bytes)
 {
-    copy_budget_ = bytes;
-    vol12_failed_ = apron_failed_ = apron_perm_failed_ = false;          // a new budget re-arms what an old one refused
+    copies_.setBudget(bytes);                                            // a new budget re-arms what an old one refused
     if (device_ < 0 || bytes == kCopyBudgetAuto) return;
     requireDevice("setCopyBudget");
-    // over the new budget: drop copies, the least valuable first (per-axis aprons, apron, packed copy)
-    if (copiesBytes() > bytes) check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
-    if (copiesBytes() > bytes) for (void *&q : d_apron_perm_) if (q) { (void)hipFree(q); q = nullptr; }
-    if (copiesBytes() > bytes && d_apron_) { (void)hipFree(d_apron_); d_apron_ = nullptr; apron_bytes_ = 0; }
-    if (copiesBytes() > bytes && d_vol12_) { (void)hipFree(d_vol12_); d_vol12_ = nullptr; vol12_bytes_ = 0; }
+    copies_.trimToBudget(stream());
 }
 
 void RendererCore::residentBytes(uint64_t &volume, uint64_t &copies, uint64_t &other) const
 {
-    volume = (uint64_t)vol_alloc_bytes_;
-    copies = copiesBytes();
-    const uint64_t px = (uint64_t)framebuffer_size[0] * (uint64_t)framebuffer_size[1];
-    other = (d_fb_ ? px * 16 : 0) + (d_tf_ ? 256 * 16 : 0) + (uint64_t)spp_capacity_ * 4 + (d_scratch_ ? 264 * 4 : 0) +
-            (d_skip_grid_ ? (uint64_t)skip_grid_cells_ * 2 : 0) + (uint64_t)loaded_alloc_bytes_ + meshBytes() + (uint64_t)rgba8_capacity_ + (uint64_t)present_capacity_ * kPresentSlots +
-            ((uint64_t)tile_table_capacity_ + (uint64_t)tile_table_tall_capacity_ + (uint64_t)tile_table_small_capacity_ + (uint64_t)tile_work_capacity_) * 4;
+    volume = d_vol_.bytes();
+    copies = copies_.copiesBytes();
+    other = d_fb_.bytes() + d_tf_.bytes() + d_spp_.bytes() + d_scratch_.bytes() + d_depth_.bytes() + d_values_.bytes() + copies_.skipGridBytes() +
+            d_loaded_.bytes() + meshBytes() + d_rgba8_.bytes() + d_tile_table_.bytes() + d_tile_table_tall_.bytes() + d_tile_table_small_.bytes() + d_tile_work_.bytes();
+    for (const auto &q : d_present_) other += q.bytes();
 }
 
 // Exact empty-space skipping (vr_set_skip_empty): the fast kernel may skip a batch of
@@ -1483,11 +1007,11 @@ void RendererCore::refreshSkipGrid(FrameParams &P, LaunchConfig &L)
     // nothing to skip at this threshold (a window that starts at the data's floor): the launch takes the instances without
     // skipping -- theirs are the leaner loops (staged TRILINEAR 3.8 %, its tiles on global taps 20 %, the NEAREST kernels a
     // workgroup of occupancy).  A host comparison against the grid's smallest cell: no device work, no synchronisation per frame.
-    if (thresh < (int)skip_grid_min_) return;
+    if (thresh < (int)copies_.skipGridMin()) return;
     P.skip_empty = 1;
     P.skip_thresh = thresh;
     P.cnx = (int32_t)cnx; P.cny = (int32_t)cny; P.cnz = (int32_t)cnz;
-    L.skip_grid = d_skip_grid_;
+    L.skip_grid = copies_.skipGrid();
     L.skip_grid_bytes = (uint32_t)(cells * sizeof(uint16_t));
 }
 
@@ -1524,24 +1048,7 @@ bool RendererCore::ensureSkipGrid()
     const uint32_t cnx = (uint32_t)(nx + 7) / 8, cny = (uint32_t)(ny + 7) / 8, cnz = (uint32_t)(nz + 7) / 8;
     const size_t cells = (size_t)cnx * cny * cnz;
     if (cells * 2 >= (1ull << 32) || cnx >= (1u << 24) || (uint64_t)cny * cnz >= (1u << 24)) return false;
-    if (!d_skip_grid_) {
-        uint16_t *tmp = nullptr;
-        check(hipMalloc(reinterpret_cast<void **>(&tmp), std::max<size_t>(cells * sizeof(uint16_t), 8)), "hipMalloc(skip grid tmp)");   // (also holds the one-word minimum below)
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_skip_grid_), cells * sizeof(uint16_t));
-        if (e == hipSuccess)
-            e = launch_build_skip_grid(d_vol_, res_bytes_, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, vol_layout_,
-                                       bricksX(nx), bricksY(ny), tmp, d_skip_grid_, stream());
-        // ... and its smallest cell, into the scratch cell grid (one word), read back with the build's own synchronisation
-        unsigned gmin = 0;
-        if (e == hipSuccess) e = launch_min_cell(d_skip_grid_, (uint64_t)cells, reinterpret_cast<unsigned *>(tmp), stream());
-        if (e == hipSuccess) e = hipMemcpyAsync(&gmin, tmp, sizeof(gmin), hipMemcpyDeviceToHost, stream());
-        if (e == hipSuccess) e = hipStreamSynchronize(stream());
-        (void)hipFree(tmp);
-        if (e != hipSuccess && d_skip_grid_) { (void)hipFree(d_skip_grid_); d_skip_grid_ = nullptr; }
-        check(e, "build skip grid");
-        skip_grid_cells_ = cells;
-        skip_grid_min_ = gmin;
-    }
+    copies_.ensureSkipGrid(residentVolume(), cells);
     return true;
 }
 
@@ -1586,14 +1093,10 @@ void RendererCore::refreshTileSchedule(const FrameParams &P, LaunchConfig &L)
             // a seventh of a sampled one in both kernel families)
             auto estimate = [&](unsigned tw, unsigned th, std::vector<float> &out) {
                 const size_t n = (size_t)((P.img_w + (int)tw - 1) / (int)tw) * (size_t)((rows + (int)th - 1) / (int)th);
-                if (2 * n > tile_work_capacity_) {
-                    if (d_tile_work_) { check(hipFree(d_tile_work_), "hipFree(tile work)"); d_tile_work_ = nullptr; }
-                    check(hipMalloc(reinterpret_cast<void **>(&d_tile_work_), 2 * n * sizeof(float)), "hipMalloc(tile work)");
-                    tile_work_capacity_ = 2 * n;
-                }
-                check(launch_tile_visible_work(P, L.skip_grid, rows, tw, th, 0.15f, filter == 1 ? 1 : 0, d_tile_work_, stream()), "tile_visible_work_kernel");
+                d_tile_work_.ensure(2 * n, "tile work");
+                check(launch_tile_visible_work(P, L.skip_grid, rows, tw, th, 0.15f, filter == 1 ? 1 : 0, d_tile_work_.get(), stream()), "tile_visible_work_kernel");
                 std::vector<float> both(2 * n);
-                check(hipMemcpyAsync(both.data(), d_tile_work_, 2 * n * sizeof(float), hipMemcpyDeviceToHost, stream()), "hipMemcpy(tile work)");
+                check(hipMemcpyAsync(both.data(), d_tile_work_.get(), 2 * n * sizeof(float), hipMemcpyDeviceToHost, stream()), "hipMemcpy(tile work)");
                 check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
                 out.resize(n);
                 for (size_t t = 0; t < n; t++) out[t] = both[2 * t + 1] > 0.0f ? std::min(both[2 * t] / both[2 * t + 1], 1.0f) : 1.0f;   // cost with skipping / without
@@ -1605,36 +1108,32 @@ void RendererCore::refreshTileSchedule(const FrameParams &P, LaunchConfig &L)
         tile_active_ = buildTileSchedule(P, rows, table, &tile_longest_, kFastTileH, kFastTileW, skip_order ? work.data() : nullptr);
         // synchronous copies: the tables are pageable temporaries
         check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
-        auto upload = [&](uint32_t *&d, size_t &capacity, size_t &blocks, const std::vector<uint32_t> &t) {
-            if (t.size() > capacity) {
-                if (d) { check(hipFree(d), "hipFree(tile table)"); d = nullptr; }
-                check(hipMalloc(reinterpret_cast<void **>(&d), t.size() * sizeof(uint32_t)), "hipMalloc(tile table)");
-                capacity = t.size();
-            }
-            if (!t.empty()) check(hipMemcpy(d, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy(tile table)");
+        auto upload = [&](DeviceBuffer<uint32_t> &d, size_t &blocks, const std::vector<uint32_t> &t) {
+            d.ensure(t.size(), "tile table");
+            if (!t.empty()) check(hipMemcpy(d.get(), t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy(tile table)");
             blocks = t.size();
         };
-        upload(d_tile_table_, tile_table_capacity_, tile_table_blocks_, table);
+        upload(d_tile_table_, tile_table_blocks_, table);
         tile_table_tall_blocks_ = 0;
         if (need32) {
             std::vector<uint32_t> tall;
             (void)buildTileSchedule(P, rows, tall, nullptr, 32u, 16u, skip_order ? work_tall.data() : nullptr);
-            upload(d_tile_table_tall_, tile_table_tall_capacity_, tile_table_tall_blocks_, tall);
+            upload(d_tile_table_tall_, tile_table_tall_blocks_, tall);
         }
         tile_table_small_blocks_ = 0;
         if (need16) {
             std::vector<uint32_t> small;
             tile_active_small_ = buildTileSchedule(P, rows, small, nullptr, 16u, 16u, skip_order ? work_small.data() : nullptr);
-            upload(d_tile_table_small_, tile_table_small_capacity_, tile_table_small_blocks_, small);
+            upload(d_tile_table_small_, tile_table_small_blocks_, small);
         }
         tile_table_key_ = shape_key;
         tile_table_skip_sig_ = skip_sig;
         std::memcpy(tile_table_cam_, P.cam, sizeof(tile_table_cam_));
     }
-    L.tile_table = d_tile_table_;
+    L.tile_table = d_tile_table_.get();
     L.tile_table_blocks = (uint32_t)tile_table_blocks_;
-    if (need32 && tile_table_tall_blocks_ > 0) { L.tile_table_tall = d_tile_table_tall_; L.tile_table_tall_blocks = (uint32_t)tile_table_tall_blocks_; }
-    if (need16 && tile_table_small_blocks_ > 0) { L.tile_table_small = d_tile_table_small_; L.tile_table_small_blocks = (uint32_t)tile_table_small_blocks_; }
+    if (need32 && tile_table_tall_blocks_ > 0) { L.tile_table_tall = d_tile_table_tall_.get(); L.tile_table_tall_blocks = (uint32_t)tile_table_tall_blocks_; }
+    if (need16 && tile_table_small_blocks_ > 0) { L.tile_table_small = d_tile_table_small_.get(); L.tile_table_small_blocks = (uint32_t)tile_table_small_blocks_; }
     // Kernel choice per launch (all bit-identical; measured on cfg3 after the checked-head fix, tools/pose_sweep.py and
     // tools/shard_ms.py; `aligned` = central ray within ~23 degrees of a volume axis):
     //   * relay kernel (4 wavefronts per 8x8 tile) for launches far from filling the chip -- fewer than 256 active
@@ -1707,8 +1206,8 @@ hipError_t RendererCore::launchKernel(const FrameParams &P, const LaunchConfig &
         A.mode = reslice_mode_;
         A.n = reslice_n_;
         A.hu_offset = (datasize_bytes == 2 && (quirks & kQuirkU16Offset)) ? 1 : 0;
-        A.values = d_values_;
-        return launch_reslice(P, L, A, d_vol_, d_tf_, fb, spp, stream(), &last_kernel_);
+        A.values = d_values_.get();
+        return launch_reslice(P, L, A, d_vol_.get(), d_tf_.get(), fb, spp, stream(), &last_kernel_);
     }
     if (shadeFrame()) {
         ShadeArgs A;
@@ -1717,14 +1216,14 @@ hipError_t RendererCore::launchKernel(const FrameParams &P, const LaunchConfig &
         while ((1 << A.spec_squarings) < shade_shininess_) A.spec_squarings++;
         A.skip_grid = shade_skip_grid_;
         A.skip_thresh = shade_skip_thresh_;
-        return launch_raymarch_shade(P, L, A, d_vol_, d_tf_, fb, spp, stream(), &last_kernel_);
+        return launch_raymarch_shade(P, L, A, d_vol_.get(), d_tf_.get(), fb, spp, stream(), &last_kernel_);
     }
-    if (!iso_enable_) return launch_raymarch(P, L, d_vol_, d_tf_, fb, spp, stream(), &last_kernel_);
+    if (!iso_enable_) return launch_raymarch(P, L, d_vol_.get(), d_tf_.get(), fb, spp, stream(), &last_kernel_);
     IsoArgs A;
     A.iso_s = isoStored();
-    A.depth = d_depth_;
+    A.depth = d_depth_.get();
     A.skip_grid = iso_skip_grid_;
-    return launch_raymarch_iso(P, L, A, d_vol_, d_tf_, fb, spp, stream(), &last_kernel_);
+    return launch_raymarch_iso(P, L, A, d_vol_.get(), d_tf_.get(), fb, spp, stream(), &last_kernel_);
 }
 
 // iso_s = float(iso + 1000) for 16-bit data under VR_QUIRK_U16_OFFSET (the window's own offset, setMinVal), float(iso) otherwise
@@ -1740,7 +1239,7 @@ void RendererCore::readDepth(float *depth, size_t n_floats)
     if (depth_rows_ < 0 || !d_depth_) throw std::invalid_argument("readDepth: no isosurface frame has been rendered");
     const size_t n = (size_t)depth_rows_ * (size_t)depth_w_;
     if (!depth || n_floats < n) throw std::invalid_argument("readDepth: buffer too small");
-    check(hipMemcpyAsync(depth, d_depth_, n * sizeof(float), hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H depth)");
+    check(hipMemcpyAsync(depth, d_depth_.get(), n * sizeof(float), hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H depth)");
     check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
 }
 
@@ -1794,7 +1293,7 @@ void RendererCore::readResliceValues(float *values, size_t n_floats)
     requireDevice("readResliceValues");
     const size_t n = (size_t)values_rows_ * (size_t)values_w_;
     if (!values || n_floats < n) throw std::invalid_argument("readResliceValues: buffer too small");
-    check(hipMemcpyAsync(values, d_values_, n * sizeof(float), hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H values)");
+    check(hipMemcpyAsync(values, d_values_.get(), n * sizeof(float), hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H values)");
     check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
 }
 
@@ -1815,15 +1314,11 @@ void RendererCore::countSamples(uint64_t *total, uint32_t *per_pixel, size_t n_p
     requireDevice("countSamples");
     const size_t n = (size_t)framebuffer_size[0] * (size_t)framebuffer_size[1];
     if (per_pixel && n_pixels < n) throw std::invalid_argument("countSamples: per_pixel buffer too small");
-    if (spp_capacity_ < n) {
-        if (d_spp_) { check(hipFree(d_spp_), "hipFree(spp)"); d_spp_ = nullptr; }
-        check(hipMalloc(reinterpret_cast<void **>(&d_spp_), n * sizeof(uint32_t)), "hipMalloc(spp)");
-        spp_capacity_ = n;
-    }
-    check(hipMemsetAsync(d_spp_, 0, n * sizeof(uint32_t), stream()), "hipMemset(spp)");
-    launch(d_spp_);
+    d_spp_.ensure(n, "spp");
+    check(hipMemsetAsync(d_spp_.get(), 0, n * sizeof(uint32_t), stream()), "hipMemset(spp)");
+    launch(d_spp_.get());
     std::vector<uint32_t> host(n);
-    check(hipMemcpyAsync(host.data(), d_spp_, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()), "hipMemcpy(spp)");
+    check(hipMemcpyAsync(host.data(), d_spp_.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()), "hipMemcpy(spp)");
     check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
     uint64_t sum = 0;
     for (uint32_t v : host) sum += v;
@@ -1853,13 +1348,9 @@ void RendererCore::readPixelsRGBA8(uint8_t *rgba8, size_t n_bytes)
         throw std::invalid_argument("readPixelsRGBA8: the external target is compact and/or (grey, alpha): it does not hold fb_w x fb_h RGBA32F pixels");
     const void *src = framebufferDevice();
     if (!src) throw std::runtime_error("readPixelsRGBA8: no framebuffer");
-    if (rgba8_capacity_ < n * 4) {
-        if (d_rgba8_) { (void)hipFree(d_rgba8_); d_rgba8_ = nullptr; rgba8_capacity_ = 0; }
-        check(hipMalloc(&d_rgba8_, n * 4), "hipMalloc(rgba8)");
-        rgba8_capacity_ = n * 4;
-    }
-    check(launch_to_rgba8(src, d_rgba8_, n, stream()), "to_rgba8_kernel");
-    check(hipMemcpyAsync(rgba8, d_rgba8_, n * 4, hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H rgba8)");
+    d_rgba8_.ensure(n * 4, "rgba8");
+    check(launch_to_rgba8(src, d_rgba8_.get(), n, stream()), "to_rgba8_kernel");
+    check(hipMemcpyAsync(rgba8, d_rgba8_.get(), n * 4, hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H rgba8)");
     check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
 }
 
@@ -1867,13 +1358,9 @@ void RendererCore::releasePresent()
 {
     if (present_stream_) (void)hipStreamSynchronize(present_stream_);
     for (int s = 0; s < kPresentSlots; s++) {
-        if (d_present_[s]) { (void)hipFree(d_present_[s]); d_present_[s] = nullptr; }
-        if (h_present_[s]) { (void)hipHostFree(h_present_[s]); h_present_[s] = nullptr; }
-        if (present_converted_[s]) { (void)hipEventDestroy(present_converted_[s]); present_converted_[s] = nullptr; }
-        if (present_copied_[s]) { (void)hipEventDestroy(present_copied_[s]); present_copied_[s] = nullptr; }
+        d_present_[s].reset(); h_present_[s].reset(); present_converted_[s].reset(); present_copied_[s].reset();
     }
     if (present_stream_) { (void)hipStreamDestroy(present_stream_); present_stream_ = nullptr; }
-    present_capacity_ = 0;
     present_count_ = 0;
 }
 
@@ -1888,16 +1375,14 @@ const uint8_t *RendererCore::presentRGBA8(const void *src_frame)
         src_frame = framebufferDevice();
         if (!src_frame) throw std::runtime_error("presentRGBA8: no framebuffer");
     }
-    if (present_capacity_ != n * 4) {
+    if (d_present_[kPresentSlots - 1].size() != n * 4) {     // (the last slot: a set-up that threw half way is done again)
         releasePresent();
         check(hipStreamCreateWithFlags(&present_stream_, hipStreamNonBlocking), "hipStreamCreate(present)");
         for (int s = 0; s < kPresentSlots; s++) {
-            check(hipMalloc(&d_present_[s], n * 4), "hipMalloc(present)");
-            check(hipHostMalloc(reinterpret_cast<void **>(&h_present_[s]), n * 4, hipHostMallocDefault), "hipHostMalloc(present)");
-            check(hipEventCreateWithFlags(&present_converted_[s], hipEventDisableTiming), "hipEventCreate");
-            check(hipEventCreateWithFlags(&present_copied_[s], hipEventDisableTiming), "hipEventCreate");
+            h_present_[s].alloc(n * 4, "hipHostMalloc(present)");
+            present_converted_[s].create(hipEventDisableTiming); present_copied_[s].create(hipEventDisableTiming);
+            d_present_[s].alloc(n * 4, "present");
         }
-        present_capacity_ = n * 4;
     }
     // three slots: call n converts and copies into slot n % 3 and hands out slot (n - 1) % 3, which call n + 1 leaves alone and
     // call n + 2 overwrites -- the pointer stays valid until the next-but-one call, as include/vr_core.h promises (round-3
@@ -1905,15 +1390,15 @@ const uint8_t *RendererCore::presentRGBA8(const void *src_frame)
     const int s = present_count_ % kPresentSlots;
     // the slot's previous copy (three frames ago) must have left its staging buffer before it is overwritten
     if (present_count_ >= kPresentSlots) check(hipStreamWaitEvent(stream(), present_copied_[s], 0), "hipStreamWaitEvent");
-    check(launch_to_rgba8(src_frame, d_present_[s], n, stream()), "to_rgba8_kernel");
+    check(launch_to_rgba8(src_frame, d_present_[s].get(), n, stream()), "to_rgba8_kernel");
     check(hipEventRecord(present_converted_[s], stream()), "hipEventRecord");
     check(hipStreamWaitEvent(present_stream_, present_converted_[s], 0), "hipStreamWaitEvent");
-    check(hipMemcpyAsync(h_present_[s], d_present_[s], n * 4, hipMemcpyDeviceToHost, present_stream_), "hipMemcpy(D2H present)");
+    check(hipMemcpyAsync(h_present_[s].get(), d_present_[s].get(), n * 4, hipMemcpyDeviceToHost, present_stream_), "hipMemcpy(D2H present)");
     check(hipEventRecord(present_copied_[s], present_stream_), "hipEventRecord");
     const int ready = present_count_ == 0 ? s : (s + kPresentSlots - 1) % kPresentSlots;   // the previous frame; the first call waits for its own
     present_count_++;
     check(hipEventSynchronize(present_copied_[ready]), "hipEventSynchronize");
-    return h_present_[ready];
+    return h_present_[ready].get();
 }
 
 // src/RendererCore.cpp:165-182: RGB8 read-back of the target, written top row first

@@ -14,18 +14,13 @@
 #include <vector>
 
 #include "camera.h"
+#include "device_buffer.h"
 #include "launch_tuner.h"
+#include "volume_copies.h"
 #include "vr_frame.h"
 
 namespace vr {
 
-struct HipError : std::runtime_error {
-    hipError_t code;
-    HipError(hipError_t c, const std::string &what) : std::runtime_error(what), code(c) {}
-};
-struct DeviceMemoryError : HipError {         // a device allocation a call cannot do without failed (VR_E_NOMEM)
-    using HipError::HipError;
-};
 struct NoDeviceError : std::runtime_error {
     using std::runtime_error::runtime_error;
 };
@@ -86,7 +81,7 @@ public:
     void getTransferLut(float *lut1024) const;
     void countSamples(uint64_t *total, uint32_t *per_pixel, size_t n_pixels);
     void readPixels(float *rgba, size_t n_floats);
-    void *framebufferDevice() const { return ext_fb_ ? ext_fb_ : d_fb_; }
+    void *framebufferDevice() const { return ext_fb_ ? ext_fb_ : d_fb_.get(); }
     void setStream(hipStream_t s) { user_stream_ = s; }
     hipStream_t streamHandle() const { return stream(); }     // the stream the next launch goes to
     bool greyMode() const { return tf_lut_.empty() && !iso_enable_; }   // r == g == b in every pixel (no transfer function, no isosurface; reslice and shaded composite frames without one are grey)
@@ -110,14 +105,14 @@ public:
     int lastLaunchChoice() const { return last_choice_; }     // 1 relay, 2 pipelined loop, 4 short batches, tri_slab << 3, 256: the work model is still exploring this configuration
     size_t lastPacked12Bytes() const { return last_packed12_bytes_; }
     size_t lastApronBytes() const { return last_apron_bytes_; }
-    // device memory this handle holds right now: the volume as loaded; the optional speed copies (12-bit packed copy, apron
-    // copies); everything else (targets, tables, skip grid, staging)
+    // device memory this handle holds right now, summed from its buffers: the volume being rendered; the optional speed copies
+    // (12-bit packed copy, apron copies); every other device buffer (targets, tables, skip grid, staging, the loaded volume, the mesh)
     void residentBytes(uint64_t &volume, uint64_t &copies, uint64_t &other) const;
     // upper bound on the optional copies' total bytes (vr_set_copy_budget).  kCopyBudgetAuto: allowed while the device keeps
-    // kCopyReserveBytes (and a tenth of its memory) free after the allocation.  Lowering it frees copies that no longer fit.
-    static constexpr uint64_t kCopyBudgetAuto = ~0ull, kCopyReserveBytes = 1ull << 30;
+    // VolumeCopies::kReserveBytes (and a tenth of its memory) free after the allocation.  Lowering it frees copies that no longer fit.
+    static constexpr uint64_t kCopyBudgetAuto = VolumeCopies::kBudgetAuto;
     void setCopyBudget(uint64_t bytes);
-    uint64_t copyBudget() const { return copy_budget_; }
+    uint64_t copyBudget() const { return copies_.budget(); }
     bool hasDevice() const { return device_ >= 0; }
     void warmTrilinear();                    // pre-load the staged TRILINEAR kernel's code objects (once)
     // first-hit isosurface mode (vr_set_isosurface): while on, frames are the shaded surface and its depth, whatever the MIP /
@@ -180,50 +175,47 @@ private:
     } u_;
     std::vector<float> cam_block_;           // the "UBO" contents (21 floats)
     bool cs_program_ = false;                // cs_programID != 0
+    static constexpr uint32_t kQuirkTruncGrid = 1u << 0, kQuirkU16Offset = 1u << 1;   // VR_QUIRK_*
 
     int device_ = -1;
     hipStream_t own_stream_ = nullptr, user_stream_ = nullptr;
-    hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
-    void *d_vol_ = nullptr;                  // the volume the kernels render: as loaded, or smoothed
-    size_t vol_alloc_bytes_ = 0;
-    void *d_loaded_ = nullptr;               // while d_vol_ is a smoothed volume: the loaded one (same dimensions, type and layout)
-    size_t loaded_alloc_bytes_ = 0;
+    Event ev0_, ev1_;
+    DeviceBuffer<uint8_t> d_vol_;            // the volume the kernels render: as loaded, or smoothed
+    DeviceBuffer<uint8_t> d_loaded_;         // while d_vol_ is a smoothed volume: the loaded one (same dimensions, type and layout)
     float smooth_sigma_[3] = {0.0f, 0.0f, 0.0f};
     float last_smooth_ms_ = 0.0f;
     bool mesh_valid_ = false;                // an extraction has succeeded (its mesh may be empty) and was not freed
     int32_t mesh_iso_ = 0;
     uint64_t mesh_nv_ = 0, mesh_nt_ = 0;
-    float *d_mesh_pos_ = nullptr, *d_mesh_nrm_ = nullptr;   // 3 floats a vertex
-    uint32_t *d_mesh_tri_ = nullptr;         // 3 indices a triangle
+    DeviceBuffer<float> d_mesh_pos_, d_mesh_nrm_;   // 3 floats a vertex
+    DeviceBuffer<uint32_t> d_mesh_tri_;      // 3 indices a triangle
     float last_mesh_ms_ = 0.0f;
     uint64_t meshBytes() const;              // device bytes of the mesh
+    hipError_t finishTimed(hipError_t e, float &ms);   // ends a stretch of kernels that began with ev0_ recorded, once `e` says they were all launched
     // geometry and voxel type of the volume that is RESIDENT (set only after a successful upload).
     // tex3D_dim / datasize_bytes above are GUI inputs of readVolumeData, like the reference's fields;
     // the reference's shader reads textureSize() of the uploaded texture (VolumeRenderer.cs:62), not them.
     int res_dims_[3] = {0, 0, 0};
     int res_bytes_ = 0;
     int vol_layout_ = 0;
-    float4 *d_fb_ = nullptr;
-    void *ext_fb_ = nullptr;
-    float4 *d_tf_ = nullptr;
-    uint32_t *d_spp_ = nullptr;
-    size_t spp_capacity_ = 0;
-    unsigned *d_scratch_ = nullptr;          // 4 + 256 words (+ slack)
+    DeviceBuffer<float4> d_fb_;
+    void *ext_fb_ = nullptr;                 // borrowed
+    DeviceBuffer<float4> d_tf_;
+    DeviceBuffer<uint32_t> d_spp_;
+    DeviceBuffer<unsigned> d_scratch_;       // 4 + 256 words (+ slack)
     std::vector<float> tf_lut_;              // 256 x RGBA, empty = grey ramp
     bool tf_grey_ = false;                   // every entry of tf_lut_ has r == g == b bit for bit
     int exact_min_ = 0, exact_max_ = 65535;   // exact voxel range of the resident volume
     int row_begin_ = 0, row_end_ = -1;
     bool iso_enable_ = false;
     int32_t iso_value_ = 0;
-    float *d_depth_ = nullptr;               // depth target of the iso frames (+inf where no surface; allocated on the first one)
-    size_t depth_capacity_ = 0;              // floats
+    DeviceBuffer<float> d_depth_;            // depth target of the iso frames (+inf where no surface; allocated on the first one)
     int depth_rows_ = -1, depth_w_ = 0;      // rows x width the last iso frame's depth is indexed by (-1: no iso frame yet)
     float isoStored() const;                 // the iso value in stored voxel units (the +1000 of VR_QUIRK_U16_OFFSET included)
     bool reslice_enable_ = false;
     float reslice_geom_[12] = {};            // o, du, dv, dw (vr_reslice.h: ResliceGeom)
     int reslice_mode_ = 0, reslice_n_ = 1;   // VR_SLAB_*, slab samples
-    float *d_values_ = nullptr;              // values target of the reslice frames (NaN where no sample; allocated on the first one)
-    size_t values_capacity_ = 0;             // floats
+    DeviceBuffer<float> d_values_;           // values target of the reslice frames (NaN where no sample; allocated on the first one)
     int values_rows_ = -1, values_w_ = 0;    // rows x width the last reslice frame's values are indexed by (-1: no reslice frame yet)
     bool shade_enable_ = false;
     float shade_k_[3] = {0.15f, 0.65f, 0.2f};   // ambient, diffuse, specular (the isosurface mode's constants)
@@ -233,34 +225,19 @@ private:
     bool fb_compact_ = false;
     int fb_format_ = 0;
     std::map<uint32_t, bool> cert_cache_;    // divisor bits -> certified
-    uint16_t *d_skip_grid_ = nullptr;        // dilated cell-max grid (built lazily, dropped with the volume)
-    void *d_rgba8_ = nullptr;                // RGBA8 staging of the target (readPixelsRGBA8)
-    size_t rgba8_capacity_ = 0;
+    DeviceBuffer<uint8_t> d_rgba8_;          // RGBA8 staging of the target (readPixelsRGBA8)
     static constexpr int kPresentSlots = 3;  // the frame handed out by call n (slot (n - 1) % 3) is written again by call n + 2: valid until the next-but-one call
-    void *d_present_[kPresentSlots] = {};    // presentRGBA8: device staging per slot
-    uint8_t *h_present_[kPresentSlots] = {}; // ... and pinned host frames
-    hipEvent_t present_converted_[kPresentSlots] = {}, present_copied_[kPresentSlots] = {};
+    DeviceBuffer<uint8_t> d_present_[kPresentSlots];   // presentRGBA8: device staging per slot (all of one size, or all empty)
+    PinnedBuffer h_present_[kPresentSlots];  // ... and pinned host frames
+    Event present_converted_[kPresentSlots], present_copied_[kPresentSlots];
     hipStream_t present_stream_ = nullptr;
-    size_t present_capacity_ = 0;
     int present_count_ = 0;                  // frames enqueued so far
     void releasePresent();
-    void *d_vol12_ = nullptr;                // 12-bit packed copy of the bricked u16 volume (lazily, dropped with the volume)
-    size_t vol12_bytes_ = 0;
-    bool vol12_failed_ = false;              // allocation of the packed copy failed for this volume: do not retry
-    size_t last_packed12_bytes_ = 0;         // packed copy used by the last launch (0 = none)
-    int vol12_base_ = 0;                     // the packed copy holds voxel - vol12_base_ (the dataset minimum when it was built)
+    VolumeCopies copies_;                    // the packed copy, the apron copies and the skip grid: built lazily from d_vol_, dropped with its voxels
+    ResidentVolume residentVolume() const { return {d_vol_.get(), res_dims_[0], res_dims_[1], res_dims_[2], res_bytes_, vol_layout_, exact_min_, stream()}; }
+    size_t last_packed12_bytes_ = 0, last_apron_bytes_ = 0;   // packed copy / apron copies used by the last launch (0 = none)
     void refreshPacked12(FrameParams &P, LaunchConfig &L);
-    void *d_apron_ = nullptr;                // TRILINEAR's apron copy of the volume (vr_frame.h: apron_voxels)
-    void *d_apron_perm_[2] = {nullptr, nullptr};   // the same with the bricks' planes along y / x slowest (half layers of the staged kernel; 16-bit volumes, oblique views)
-    bool apron_perm_failed_ = false;
-    size_t apron_bytes_ = 0, last_apron_bytes_ = 0;
-    bool apron_failed_ = false;
     void refreshApron(const FrameParams &P, LaunchConfig &L);
-    uint64_t copy_budget_ = kCopyBudgetAuto;
-    uint64_t copiesBytes() const;            // optional copies resident now
-    bool copyFits(uint64_t bytes) const;     // may another optional copy of `bytes` be allocated (budget / free device memory)?
-    size_t skip_grid_cells_ = 0;
-    unsigned skip_grid_min_ = 0;             // smallest cell value of the grid (read back once when it is built): a threshold below it skips nothing and the launch keeps the instances without skipping
     void refreshSkipGrid(FrameParams &P, LaunchConfig &L);
     void refuseIsoGreyAlpha() const;
     bool ensureSkipGrid();                   // build the dilated cell-max grid if it is not resident; false = the volume is too large for it
@@ -272,17 +249,14 @@ private:
     const uint16_t *shade_skip_grid_ = nullptr;   // the grid the shaded launch being prepared skips on (nullptr = no skipping) ...
     int shade_skip_thresh_ = 0;                   // ... and its threshold
     hipError_t launchKernel(const FrameParams &P, const LaunchConfig &L, float4 *fb, uint32_t *spp);   // the ray-march, the iso, the reslice or the shaded kernel
-    uint32_t *d_tile_table_ = nullptr;       // work-ordered block -> tile table (tile_schedule.h)
-    size_t tile_table_capacity_ = 0, tile_table_blocks_ = 0;
-    uint32_t *d_tile_table_tall_ = nullptr;  // the same for 16x32-pixel tiles (the staged trilinear kernel's tall shape); built with the table above
-    size_t tile_table_tall_capacity_ = 0, tile_table_tall_blocks_ = 0;
-    uint32_t *d_tile_table_small_ = nullptr; // the same for 16x16-pixel tiles (the staged trilinear kernel's four-wavefront shape)
-    size_t tile_table_small_capacity_ = 0, tile_table_small_blocks_ = 0;
+    DeviceBuffer<uint32_t> d_tile_table_;    // work-ordered block -> tile table (tile_schedule.h); grown only: *_blocks_ words of each are in use
+    DeviceBuffer<uint32_t> d_tile_table_tall_;   // the same for 16x32-pixel tiles (the staged trilinear kernel's tall shape); built with the table above
+    DeviceBuffer<uint32_t> d_tile_table_small_;  // the same for 16x16-pixel tiles (the staged trilinear kernel's four-wavefront shape)
+    size_t tile_table_blocks_ = 0, tile_table_tall_blocks_ = 0, tile_table_small_blocks_ = 0;
     unsigned tile_active_small_ = 0;
     uint64_t tile_table_key_ = 0;
     int64_t tile_table_skip_sig_ = 0;        // what the order was built for: 0 = geometric ray lengths, threshold + 1 = visible work under empty-space skipping (-1: rebuild)
-    float *d_tile_work_ = nullptr;           // per-tile cost estimates of that (scratch of refreshTileSchedule)
-    size_t tile_work_capacity_ = 0;
+    DeviceBuffer<float> d_tile_work_;        // per-tile cost estimates of that (scratch of refreshTileSchedule)
     float tile_table_cam_[21] = {};          // camera block the cached order was built for
     unsigned tile_active_ = 0;               // tiles with work in the cached schedule
     double tile_longest_ = 0.0;              // expected samples of its longest ray
@@ -293,7 +267,7 @@ private:
     // class enumerates the candidates and times the measurement launches (HIP events on the launch stream, polled without blocking)
     LaunchTuner tuner_;
     static constexpr int kTuneSlots = 12;    // asynchronous measurements that may be in flight (a burst of renderAsync calls)
-    struct TuneSlot { hipEvent_t ev0 = nullptr, ev1 = nullptr; uint64_t key = 0, gen = 0; int cand = -1; };   // cand: the candidate VALUE (bit set), not its index in the entry's shuffled order
+    struct TuneSlot { Event ev0, ev1; uint64_t key = 0, gen = 0; int cand = -1; };   // cand: the candidate VALUE (bit set), not its index in the entry's shuffled order
     TuneSlot tune_slot_[kTuneSlots];
     int tune_head_ = 0, tune_count_ = 0;     // ring of in-flight slots: oldest at tune_head_
     LaunchTuner::Pick tune_pick_;            // the tuner's decision for the launch being prepared (measure: it is a measurement)
@@ -304,11 +278,11 @@ private:
 
     hipStream_t stream() const { return user_stream_ ? user_stream_ : own_stream_; }
     void requireDevice(const char *what) const;
-    void check(hipError_t e, const char *what) const;
+    void check(hipError_t e, const char *what) const { hipCheck(e, what); }
     void freeVolume();
     void dropDerived();                      // everything built from the voxels of d_vol_: packed copy, apron copies, skip grid, the tile order under skipping
     void allocVolume(int nx, int ny, int nz, int bytes, int layout);
-    void *allocVolumeBuffer(int nx, int ny, int nz, int bytes, int layout, size_t &alloc_bytes);   // allocVolume's storage contract: zeroed brick padding, the slack slab
+    DeviceBuffer<uint8_t> allocVolumeBuffer(int nx, int ny, int nz, int bytes, int layout);   // allocVolume's storage contract: zeroed brick padding, the slack slab
     void smoothPasses(const void *src, void *dst, const float sigma[3]);
     size_t storageVoxels(int nx, int ny, int nz, int layout) const;
     void afterVolumeLoaded(const std::string &name);
@@ -317,7 +291,7 @@ private:
     void buildFrame(FrameParams &P, LaunchConfig &L);
     float4 *prepareLaunch(FrameParams &P, LaunchConfig &L);
     void setSkipCells(FrameParams &P) const;
-    void growFloatTarget(float *&d, size_t &capacity, int fill, const char *name);
+    void growFloatTarget(DeviceBuffer<float> &d, int fill, const char *name);
     void launch(uint32_t *spp);
     void updateWorkgroups();
     void setMessage(const std::string &t, const std::string &m) { title = t; msg = m; }

@@ -1,0 +1,302 @@
+// volume_ops.cpp -- RendererCore members that compute on the resident volume outside a frame: Gaussian smoothing
+// (vr_smooth_volume) and isosurface extraction with its mesh (vr_extract_isosurface; section 1.5).
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+
+#include "renderer_core.h"
+#include "vr_mesh.h"
+#include "vr_smooth.h"
+
+namespace vr {
+
+// The kernels of smoothPasses / extractIsosurface run between ev0_ and ev1_ (the events render() times frames with): records ev1_
+// unless `e` says a launch failed, waits for the stream either way, and adds the elapsed time to `ms`
+hipError_t RendererCore::finishTimed(hipError_t e, float &ms)
+{
+    if (e == hipSuccess) e = hipEventRecord(ev1_, stream());
+    const hipError_t es = hipStreamSynchronize(stream());
+    if (e == hipSuccess) e = es;
+    float t = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&t, ev0_, ev1_);
+    ms += t;
+    return e;
+}
+
+// ---------------------------------------------------------------- smoothing (vr_smooth_volume)
+// The passes of one smoothing, src -> dst (both allocVolume storage in vol_layout_): x, then y, then z, an axis with sigma 0
+// skipped.  With one pass the voxels go straight from src to dst.  With more, fp32 planes carry the intermediates: the whole
+// volume's where one buffer fits the workspace bound, else z slabs -- the passes before z then also cover the r_z planes on
+// either side of the slab, which the z pass reads (every plane of a slab is computed from the same inputs by the same
+// operations as in one piece: the result does not depend on the slab size).  The buffers are freed before this returns.
+void RendererCore::smoothPasses(const void *src, void *dst, const float sigma[3])
+{
+    const int nx = res_dims_[0], ny = res_dims_[1], nz = res_dims_[2];
+    float w[3][2 * kSmoothMaxRadius + 1];
+    int r[3] = {0, 0, 0}, axes[3], n = 0;
+    for (int a = 0; a < 3; a++)
+        if (sigma[a] > 0.0f) {
+            if (!smooth_weights(sigma[a], w[a], 2 * kSmoothMaxRadius + 1, &r[a])) throw std::invalid_argument("smoothVolume: bad sigma");
+            axes[n++] = a;
+        }
+    SmoothPass S = {};
+    S.bytes_per_voxel = res_bytes_; S.layout = vol_layout_;
+    S.nx = nx; S.ny = ny; S.nz = nz;
+    auto pass = [&](int a, const void *in, bool in_float, void *out, bool out_float, int buf_z0, int buf_planes, int z0, int z1) {
+        S.in = in; S.out = out; S.in_float = in_float; S.out_float = out_float;
+        S.in_z0 = S.out_z0 = buf_z0; S.in_planes = S.out_planes = buf_planes;
+        S.axis = a; S.z_begin = z0; S.z_end = z1; S.radius = r[a]; S.weights = w[a];
+        return launch_smooth_pass(S, stream());
+    };
+    last_smooth_ms_ = 0.0f;                               // (lastSmoothMs: the passes, first launch to last)
+    if (n == 1) {
+        hipError_t e = hipEventRecord(ev0_, stream());
+        if (e == hipSuccess) e = pass(axes[0], src, false, dst, false, 0, 0, 0, nz);
+        check(finishTimed(e, last_smooth_ms_), "smooth kernel");
+        return;
+    }
+    const int rz = sigma[2] > 0.0f ? r[2] : 0;           // planes either side of a slab the passes before z must cover
+    const uint64_t plane_bytes = (uint64_t)nx * (uint64_t)ny * sizeof(float);
+    const int nbuf = n - 1;
+    uint64_t bound = smooth_workspace_limit;
+    if (bound == 0) {
+        bound = 2ull << 30;
+        uint64_t room = 0;
+        if (VolumeCopies::freeBeyondReserve(room)) bound = std::min<uint64_t>(bound, room / (uint64_t)nbuf);
+    }
+    uint64_t planes = std::min<uint64_t>(bound / plane_bytes, (uint64_t)nz);
+    if (planes < (uint64_t)std::min(nz, 2 * rz + 1))
+        throw DeviceMemoryError(hipErrorOutOfMemory, "smoothVolume: the workspace cannot hold one slab of fp32 planes");
+    const int slab = planes >= (uint64_t)nz ? nz : (int)planes - 2 * rz;      // output planes per slab
+    DeviceBuffer<uint8_t> buf[2];
+    for (int b = 0; b < nbuf; b++) buf[b].allocOrNoMemory(planes * plane_bytes, "smoothVolume: hipMalloc(fp32 planes)");
+    hipError_t e = hipEventRecord(ev0_, stream());
+    for (int s0 = 0; s0 < nz && e == hipSuccess; s0 += slab) {
+        const int s1 = std::min(s0 + slab, nz), e0 = std::max(s0 - rz, 0), e1 = std::min(s1 + rz, nz);
+        const void *in = src;
+        for (int k = 0; k < n && e == hipSuccess; k++) {
+            const bool last = k == n - 1;
+            void *out = last ? dst : buf[k & 1].get();
+            e = pass(axes[k], in, k > 0, out, !last, e0, e1 - e0, last ? s0 : e0, last ? s1 : e1);
+            in = out;
+        }
+    }
+    check(finishTimed(e, last_smooth_ms_), "smooth kernel");
+}
+
+void RendererCore::smoothVolume(float sigma_x, float sigma_y, float sigma_z)
+{
+    const float sigma[3] = {sigma_x, sigma_y, sigma_z};
+    for (float s : sigma)
+        if (!std::isfinite(s) || s < 0.0f || s > kSmoothMaxSigma) throw std::invalid_argument("smoothVolume: every sigma must be finite and in [0, 8] voxels");
+    requireDevice("smoothVolume");
+    if (!d_vol_) throw std::runtime_error("smoothVolume: no dataset loaded");
+    check(hipStreamSynchronize(stream()), "hipStreamSynchronize");      // frames in flight read the buffers replaced below
+    const bool off = sigma_x == 0.0f && sigma_y == 0.0f && sigma_z == 0.0f;
+    if (off && !d_loaded_) return;                                       // rendering the loaded volume already
+    // The volume to render next: the loaded one again, or a new buffer the passes fill (freed with `next` if they throw, which waits
+    // for them).  It is swapped in first and swapped back if the range scan fails, so a call that throws leaves the handle as it was.
+    DeviceBuffer<uint8_t> next;
+    if (!off) {
+        try {
+            next = allocVolumeBuffer(res_dims_[0], res_dims_[1], res_dims_[2], res_bytes_, vol_layout_);
+        } catch (const HipError &err) {
+            (void)hipGetLastError();
+            throw DeviceMemoryError(err.code, std::string("smoothVolume: ") + err.what());
+        }
+        smoothPasses(d_loaded_ ? d_loaded_.get() : d_vol_.get(), next.get(), sigma);
+    }
+    DeviceBuffer<uint8_t> &other = off ? d_loaded_ : next;               // after the swap: the volume rendered until now
+    const int keep[8] = {min_val, max_val, min_dataset_val, max_dataset_val, exact_min_, exact_max_, 0, 0};
+    d_vol_.swap(other);
+    try {
+        scanDatasetRange();                                              // the ranges of the rendered volume; it also sets the window from the data ...
+    } catch (...) {
+        (void)hipStreamSynchronize(stream());
+        d_vol_.swap(other);
+        min_val = keep[0]; max_val = keep[1]; min_dataset_val = keep[2]; max_dataset_val = keep[3]; exact_min_ = keep[4]; exact_max_ = keep[5];
+        throw;
+    }
+    min_val = keep[0]; max_val = keep[1];                                // ... which is the user's and stays; no message, camera and uniforms untouched
+    if (off) d_loaded_.reset();                                          // the smoothed volume
+    else if (!d_loaded_) d_loaded_ = std::move(next);                    // (else `next` frees the earlier smoothing result)
+    for (int a = 0; a < 3; a++) smooth_sigma_[a] = sigma[a];
+    dropDerived();                                                       // what a load leaves behind for new voxels
+}
+
+// ---------------------------------------------------------------- extraction (vr_extract_isosurface)
+uint64_t RendererCore::meshBytes() const { return d_mesh_pos_.bytes() + d_mesh_nrm_.bytes() + d_mesh_tri_.bytes(); }
+
+void RendererCore::freeMesh()
+{
+    d_mesh_pos_.reset(); d_mesh_nrm_.reset(); d_mesh_tri_.reset();
+    mesh_nv_ = mesh_nt_ = 0;
+    mesh_valid_ = false;
+}
+
+// Two passes over the z slabs the workspace allows.  The first counts and scans every slab and keeps only the slabs' totals: the
+// mesh's size is known, and checked, before anything of it is allocated.  The second counts and scans a slab again (not where one
+// slab is the whole volume: its arrays are still there) and emits its vertices and triangles at the bases the totals give; a slab
+// without a vertex is skipped.  The arrays are freed before this returns; the previous mesh is replaced only at the very end.
+void RendererCore::extractIsosurface(int32_t iso, uint64_t *n_vertices, uint64_t *n_triangles)
+{
+    requireDevice("extractIsosurface");
+    if (!d_vol_) throw std::runtime_error("extractIsosurface: no dataset loaded");
+    const int nx = res_dims_[0], ny = res_dims_[1], nz = res_dims_[2];
+    uint64_t nv = 0, nt = 0;
+    DeviceBuffer<float> pos, nrm;                        // the new mesh: moved into the handle at the very end
+    DeviceBuffer<uint32_t> tri;
+    float ms = 0.0f;
+    if (nx >= 2 && ny >= 2 && nz >= 2) {
+        const uint64_t plane = (uint64_t)nx * (uint64_t)ny;
+        uint64_t bound = mesh_workspace_limit;
+        if (bound == 0) {
+            bound = 2ull << 30;
+            uint64_t room = 0;
+            if (VolumeCopies::freeBeyondReserve(room)) bound = std::min<uint64_t>(bound, room);
+        }
+        // planes the arrays hold: a slab's own ones and the plane after them
+        uint64_t planes = std::min<uint64_t>(std::min<uint64_t>(bound / (kMeshBytesPerVoxel * plane), kMeshMaxSlabVoxels / plane), (uint64_t)nz);
+        if (planes < 2) throw DeviceMemoryError(hipErrorOutOfMemory, "extractIsosurface: the workspace cannot hold two planes of per-voxel counts");
+        const int slab = planes >= (uint64_t)nz ? nz : (int)planes - 1;
+        const int nslabs = (nz + slab - 1) / slab;
+        const uint64_t words = planes * plane + 1;
+        const size_t temp_bytes = mesh_scan_temp_bytes(words);
+        DeviceBuffer<uint64_t> scan, slab_totals;        // this call's arrays: freed when it returns or throws
+        DeviceBuffer<uint8_t> mask, temp;
+        scan.allocOrNoMemory(words, "extractIsosurface: hipMalloc(offsets)");
+        mask.allocOrNoMemory(planes * plane, "extractIsosurface: hipMalloc(masks)");
+        temp.allocOrNoMemory(temp_bytes ? temp_bytes : 16, "extractIsosurface: hipMalloc(scan scratch)");
+        slab_totals.allocOrNoMemory((size_t)nslabs * 2, "extractIsosurface: hipMalloc(totals)");
+        uint64_t *const d_scan = scan.get(), *const d_totals = slab_totals.get();
+        MeshSlab S = {};
+        S.volume = d_vol_.get(); S.bytes_per_voxel = res_bytes_; S.layout = vol_layout_;
+        S.nx = nx; S.ny = ny; S.nz = nz;
+        S.iso_s = (float)((int64_t)iso + (datasize_bytes == 2 && (quirks & kQuirkU16Offset) ? 1000 : 0));   // isoStored's rule
+        for (int a = 0; a < 3; a++) S.spacing[a] = voxel_size[a];
+        S.scan = d_scan; S.mask = mask.get();
+        auto countAndScan = [&](int s) {
+            S.z0 = s * slab; S.z1 = std::min(S.z0 + slab, nz);
+            hipError_t e = launch_mesh_count(S, stream());
+            if (e == hipSuccess) e = launch_mesh_scan(d_scan, mesh_scan_words(S), temp.get(), temp_bytes, stream());
+            return e;
+        };
+        hipError_t e = hipEventRecord(ev0_, stream());
+        for (int s = 0; s < nslabs && e == hipSuccess; s++) {
+            e = countAndScan(s);
+            // vertices of the slab's own planes: the offset of the first voxel after them; triangles: the last word's offset
+            if (e == hipSuccess) e = hipMemcpyAsync(d_totals + 2 * s, d_scan + (uint64_t)(S.z1 - S.z0) * plane, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream());
+            if (e == hipSuccess) e = hipMemcpyAsync(d_totals + 2 * s + 1, d_scan + mesh_scan_words(S) - 1, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream());
+        }
+        check(finishTimed(e, ms), "extraction kernels (count)");
+        std::vector<uint64_t> totals((size_t)nslabs * 2);
+        check(hipMemcpy(totals.data(), d_totals, totals.size() * sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy(D2H totals)");
+        std::vector<uint64_t> vbase((size_t)nslabs), tbase((size_t)nslabs);
+        for (int s = 0; s < nslabs; s++) {
+            vbase[s] = nv; tbase[s] = nt;
+            nv += totals[2 * s] & 0xffffffffull;
+            nt += totals[2 * s + 1] >> 32;
+        }
+        if (nv > 0xffffffffull || nt > 0xffffffffull) {
+            setMessage("Error!", "The isosurface has " + std::to_string(nv) + " vertices and " + std::to_string(nt) +
+                                     " triangles: more than 32-bit indices address. Smooth the volume or choose another iso value.");
+            throw std::invalid_argument("extractIsosurface: more than 2^32 - 1 vertices or triangles");
+        }
+        if (nv > 0) {
+            pos.allocOrNoMemory(nv * 3, "extractIsosurface: hipMalloc(positions)");
+            nrm.allocOrNoMemory(nv * 3, "extractIsosurface: hipMalloc(normals)");
+        }
+        if (nt > 0) tri.allocOrNoMemory(nt * 3, "extractIsosurface: hipMalloc(triangles)");
+        if (nv > 0) {
+            S.positions = pos.get(); S.normals = nrm.get(); S.triangles = tri.get();
+            e = hipEventRecord(ev0_, stream());
+            for (int s = 0; s < nslabs && e == hipSuccess; s++) {
+                if ((totals[2 * s] & 0xffffffffull) == 0) continue;
+                if (nslabs > 1) e = countAndScan(s);
+                else { S.z0 = 0; S.z1 = nz; }
+                S.vertex_base = vbase[s]; S.triangle_base = tbase[s];
+                if (e == hipSuccess) e = launch_mesh_emit(S, stream());
+            }
+            check(finishTimed(e, ms), "extraction kernels (emit)");
+        }
+    }
+    freeMesh();
+    d_mesh_pos_ = std::move(pos); d_mesh_nrm_ = std::move(nrm); d_mesh_tri_ = std::move(tri);
+    mesh_nv_ = nv; mesh_nt_ = nt; mesh_iso_ = iso; mesh_valid_ = true;
+    last_mesh_ms_ = ms;
+    if (n_vertices) *n_vertices = nv;
+    if (n_triangles) *n_triangles = nt;
+}
+
+void RendererCore::meshInfo(int32_t *iso, uint64_t *n_vertices, uint64_t *n_triangles) const
+{
+    if (!mesh_valid_) throw std::invalid_argument("meshInfo: no isosurface has been extracted");
+    if (iso) *iso = mesh_iso_;
+    if (n_vertices) *n_vertices = mesh_nv_;
+    if (n_triangles) *n_triangles = mesh_nt_;
+}
+
+void RendererCore::readMesh(float *positions, float *normals, uint32_t *triangles, uint64_t vertex_capacity, uint64_t triangle_capacity)
+{
+    if (!mesh_valid_) throw std::invalid_argument("readMesh: no isosurface has been extracted");
+    if (((positions || normals) && vertex_capacity < mesh_nv_) || (triangles && triangle_capacity < mesh_nt_))
+        throw std::invalid_argument("readMesh: buffer too small");
+    requireDevice("readMesh");
+    if (positions && mesh_nv_) check(hipMemcpyAsync(positions, d_mesh_pos_.get(), mesh_nv_ * 12, hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H positions)");
+    if (normals && mesh_nv_) check(hipMemcpyAsync(normals, d_mesh_nrm_.get(), mesh_nv_ * 12, hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H normals)");
+    if (triangles && mesh_nt_) check(hipMemcpyAsync(triangles, d_mesh_tri_.get(), mesh_nt_ * 12, hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H triangles)");
+    check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
+}
+
+// "stl": binary STL, the facet normal the unit cross product of the stored positions in double, (0, 0, 0) for a zero-area
+// triangle, attribute word 0.  "ply": binary_little_endian 1.0, x y z nx ny nz as float, faces uchar uint.
+void RendererCore::saveMesh(const std::string &fn, const std::string &ext)
+{
+    if (!mesh_valid_) throw std::invalid_argument("saveMesh: no isosurface has been extracted");
+    if (ext != "stl" && ext != "ply") throw std::invalid_argument("saveMesh: the extension must be \"stl\" or \"ply\"");
+    std::vector<float> pos((size_t)mesh_nv_ * 3), nrm((size_t)mesh_nv_ * 3);
+    std::vector<uint32_t> tri((size_t)mesh_nt_ * 3);
+    readMesh(pos.data(), ext == "ply" ? nrm.data() : nullptr, tri.data(), mesh_nv_, mesh_nt_);
+    FILE *f = std::fopen(fn.c_str(), "wb");
+    if (!f) throw IoError("saveMesh: cannot open " + fn);
+    bool ok = true;
+    auto put = [&](const void *p, size_t n) { ok = ok && (n == 0 || std::fwrite(p, 1, n, f) == n); };
+    if (ext == "stl") {
+        char header[80] = "binary STL written by vr_save_mesh";
+        const uint32_t count = (uint32_t)mesh_nt_;
+        put(header, sizeof(header));
+        put(&count, 4);
+        for (uint64_t t = 0; t < mesh_nt_ && ok; t++) {
+            const float *p0 = &pos[3 * (size_t)tri[3 * t]], *p1 = &pos[3 * (size_t)tri[3 * t + 1]], *p2 = &pos[3 * (size_t)tri[3 * t + 2]];
+            const double u[3] = {(double)p1[0] - p0[0], (double)p1[1] - p0[1], (double)p1[2] - p0[2]};
+            const double v[3] = {(double)p2[0] - p0[0], (double)p2[1] - p0[1], (double)p2[2] - p0[2]};
+            const double c[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
+            const double len = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+            float rec[12] = {};
+            if (len > 0.0) for (int a = 0; a < 3; a++) rec[a] = (float)(c[a] / len);
+            for (int a = 0; a < 3; a++) { rec[3 + a] = p0[a]; rec[6 + a] = p1[a]; rec[9 + a] = p2[a]; }
+            const uint16_t attribute = 0;
+            put(rec, sizeof(rec));
+            put(&attribute, 2);
+        }
+    } else {
+        const std::string header = "ply\nformat binary_little_endian 1.0\ncomment isosurface at " + std::to_string(mesh_iso_) +
+                                   ", written by vr_save_mesh\nelement vertex " + std::to_string(mesh_nv_) +
+                                   "\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n"
+                                   "element face " + std::to_string(mesh_nt_) + "\nproperty list uchar uint vertex_indices\nend_header\n";
+        put(header.data(), header.size());
+        for (uint64_t v = 0; v < mesh_nv_ && ok; v++) {
+            put(&pos[3 * (size_t)v], 12);
+            put(&nrm[3 * (size_t)v], 12);
+        }
+        const uint8_t three = 3;
+        for (uint64_t t = 0; t < mesh_nt_ && ok; t++) {
+            put(&three, 1);
+            put(&tri[3 * (size_t)t], 12);
+        }
+    }
+    if (std::fclose(f) != 0) ok = false;
+    if (!ok) throw IoError("saveMesh: writing " + fn + " failed");
+}
+
+}  // namespace vr
