@@ -353,6 +353,64 @@ int vr_set_mesh_workspace(vr_handle h, uint64_t bytes);
 /* measurement aid: HIP-event time, in ms, of the kernels of the last successful vr_extract_isosurface (the counting pass plus
    the emitting pass; allocations and host work excluded); 0 before the first */
 int vr_get_mesh_ms(vr_handle h, float *ms);
+/* Connected components of the inside voxels, labelled on the device, and the extraction of only the selected ones (no
+   reference equivalent; VTK's connectivity filter, 3D Slicer's "Islands", ParaView's "Extract largest region"): at a bone
+   threshold a CT gives one skeleton, the scanner table and tens of thousands of specks; this keeps the largest pieces or drops
+   the small ones before a single triangle is written.
+   1. Inside: as step 2 of the extraction: s = (float) of the raw stored voxel of the volume being rendered (the smoothed one
+      after vr_smooth_volume); iso_s = float(iso_value + 1000) for 16-bit data under VR_QUIRK_U16_OFFSET, float(iso_value)
+      otherwise.  A voxel is INSIDE when s >= iso_s.
+   2. Adjacency: inside voxels A and B = A + e_d are adjacent for d = 0 .. 6, the extraction's seven directions (1,0,0), (0,1,0),
+      (0,0,1), (1,1,0), (1,0,1), (0,1,1), (1,1,1): with their opposites a 14-neighbourhood.  The other 12 of the 26 neighbours --
+      (1,-1,0), (1,0,-1), (0,1,-1), (1,1,-1), (1,-1,1), (-1,1,1) and their opposites -- are NOT adjacent.  A component is a class
+      of the transitive closure.  Why these: every edge of a Kuhn tetrahedron is one of the seven directions, so the inside
+      corners of any tetrahedron lie in one component, an edge that carries a vertex has exactly one inside end, and every
+      triangle of the mesh belongs to exactly one component.
+   3. Numbering: a component's FIRST VOXEL is its voxel of lowest linear index i + nx*(j + ny*k).  Components are numbered
+      1 .. n by ascending first voxel; outside voxels have label 0.  The numbering, and so every output, is the same bytes on
+      every run.  More than 2^32 - 2 components: VR_E_INVALID and a message for vr_take_message, the previous labelling kept.
+   4. Record per component (vr_read_components; entry label - 1; any pointer may be NULL; a capacity below n: VR_E_INVALID):
+      voxels (uint64), first_voxel (uint64 linear index), bbox (six int32: lo x, y, z, hi x, y, z, inclusive), selected (uint8).
+   5. Labels: one uint32 per voxel, x fastest, in linear order whatever the volume's layout (vr_read_labels: n_voxels at least
+      nx*ny*nz; vr_component_at: one voxel's).  They stay on the device and count under `other` in vr_get_resident_bytes.
+      Unlike the mesh the labelling is not a product: it belongs to the voxels and is dropped when the rendered voxels change --
+      a load, vr_set_volume, vr_generate_synthetic, vr_smooth_volume -- and by vr_free_components.  It survives vr_set_layout,
+      the window, the camera, the modes and vr_set_quirks, because it keeps its own iso_s.
+   6. Selection: after labelling every component is selected.  vr_select_components(min_voxels, keep_largest): a component is
+      selected when voxels >= min_voxels and, when keep_largest > 0, it is among the keep_largest first in the order (voxels
+      descending, label ascending).  vr_select_component_list selects exactly the listed labels (n = 0: none); a label of 0 or
+      above n: VR_E_INVALID and nothing changes.  Selection is host logic on the records; the per-voxel work stays on the device.
+   7. Filtered extraction, vr_extract_components: the mesh of vr_extract_isosurface at the labelling's iso value (and iso_s)
+      with step 2's INSIDE replaced by "INSIDE and its component is selected".  Everything else is unchanged: s, f, positions,
+      gradients and normals from the raw voxels, the vertex and triangle order, the z slabs under vr_set_mesh_workspace, the
+      2^32 - 1 limits and their errors.  It replaces the handle's mesh: vr_get_mesh_info (which reports the labelling's iso
+      value), vr_read_mesh, vr_save_mesh, vr_free_mesh and vr_get_mesh_ms serve it.  Consequences: with every component selected
+      it is vr_extract_isosurface's mesh byte for byte; otherwise it is that mesh's sub-mesh -- the kept vertices and triangles
+      in their order, the indices renumbered -- and no other byte changes.  (Zeroing the removed voxels and extracting again is
+      NOT the same: it changes the normals of kept vertices beside removed voxels, whose central differences read them.)
+      Nothing selected: the empty mesh, VR_OK.  Without a labelling: VR_E_INVALID.
+   8. Errors, as the extraction's: no volume: VR_E_INVALID; a host-only handle: VR_E_NO_DEVICE; a device allocation that fails:
+      VR_E_NOMEM; a kernel whose union-find loop hits its iteration cap (a defect, not an input): VR_E_HIP; after any of them
+      the previous labelling and mesh are still there.  The queries before the first labelling: VR_E_INVALID.  Labelling
+      changes no rendering state and queues no message on success.
+   Memory: the labels are whole-volume, with no slab path: 4 bytes a voxel, plus 8 bytes a voxel of parents while labelling a
+   volume of 2^32 - 1 voxels or more (1024^3: 4 GiB; 2048^3: 96 GiB while labelling, 32 GiB afterwards), plus 1/4 byte a voxel
+   of root bits and counts; vr_extract_components adds 1/8 byte a voxel for the selection.  VR_E_NOMEM where it does not fit.
+   vr_set_component_index_bits: aid for tests: 0 (default) automatic, 32, 64 = the parents' width for the next labelling (32 on
+   a volume it cannot number: that labelling gives VR_E_INVALID); other values: VR_E_INVALID. */
+int vr_label_components(vr_handle h, int32_t iso_value, uint64_t *n_components);
+int vr_get_components_info(vr_handle h, int32_t *iso_value, uint64_t *n_components, uint64_t *n_inside, uint64_t *n_selected);
+int vr_read_components(vr_handle h, uint64_t *voxels, uint64_t *first_voxel, int32_t *bbox6, uint8_t *selected, uint64_t capacity);
+int vr_read_labels(vr_handle h, uint32_t *labels, uint64_t n_voxels);
+int vr_component_at(vr_handle h, int i, int j, int k, uint32_t *label);
+int vr_select_components(vr_handle h, uint64_t min_voxels, uint64_t keep_largest, uint64_t *n_selected);
+int vr_select_component_list(vr_handle h, const uint32_t *labels, uint64_t n, uint64_t *n_selected);
+int vr_extract_components(vr_handle h, uint64_t *n_vertices, uint64_t *n_triangles);
+int vr_free_components(vr_handle h);
+int vr_set_component_index_bits(vr_handle h, int bits);
+/* measurement aid: HIP-event time, in ms, of the kernels of the last successful vr_label_components (tile pass, seam pass,
+   flatten, scan, labels, records; allocations, read-backs and host work excluded); 0 before the first */
+int vr_get_components_ms(vr_handle h, float *ms);
 /* kernel selection: 0 = automatic (specialised kernels when the configuration allows; launches far from filling the
    chip -- fewer than 256 active 32x16 tiles, 1024 when the view is oblique to the volume axes -- use the 4-wavefront
    relay kernel; the fast kernel runs its software-pipelined batch loop unless alpha_scale >= 0.5),

@@ -19,6 +19,7 @@
 #include "vr_reslice.h"
 #include "vr_shade.h"
 #include "vr_smooth.h"
+#include "vr_components.h"
 #include "vr_mesh.h"
 #include "vr_kernels.h"
 
@@ -152,6 +153,7 @@ bool RendererCore::loadShader(std::string fn, bool reload)
         check(launch_warm_shade(stream()), "module pre-load (shading)");
         check(launch_warm_smooth(stream()), "module pre-load (smoothing)");
         check(launch_warm_mesh(stream()), "module pre-load (extraction)");
+        check(launch_warm_components(stream()), "module pre-load (components)");
         check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
         tslab_warm_ = false;
         if (filter == 1) warmTrilinear();
@@ -197,6 +199,7 @@ void RendererCore::freeVolume()
     smooth_sigma_[0] = smooth_sigma_[1] = smooth_sigma_[2] = 0.0f;
     res_dims_[0] = res_dims_[1] = res_dims_[2] = 0; res_bytes_ = 0;
     dropDerived();
+    freeComponents();                                                    // the labelling belongs to the voxels that just went
 }
 
 void RendererCore::dropDerived()
@@ -969,7 +972,7 @@ void RendererCore::residentBytes(uint64_t &volume, uint64_t &copies, uint64_t &o
     volume = d_vol_.bytes();
     copies = copies_.copiesBytes();
     other = d_fb_.bytes() + d_tf_.bytes() + d_spp_.bytes() + d_scratch_.bytes() + d_depth_.bytes() + d_values_.bytes() + copies_.skipGridBytes() +
-            d_loaded_.bytes() + meshBytes() + d_rgba8_.bytes() + d_tile_table_.bytes() + d_tile_table_tall_.bytes() + d_tile_table_small_.bytes() + d_tile_work_.bytes();
+            d_loaded_.bytes() + meshBytes() + d_labels_.bytes() + d_rgba8_.bytes() + d_tile_table_.bytes() + d_tile_table_tall_.bytes() + d_tile_table_small_.bytes() + d_tile_work_.bytes();
     for (const auto &q : d_present_) other += q.bytes();
 }
 

@@ -155,6 +155,27 @@ public:
     // upper bound on the bytes of extractIsosurface's per-voxel arrays (vr_set_mesh_workspace; 9 bytes a voxel); 0: automatic --
     // 2 GiB or what the device has free; the extraction runs in z slabs that fit
     uint64_t mesh_workspace_limit = 0;
+    // connected components of the inside voxels (s >= iso) of the volume being rendered under the 14-neighbourhood of the
+    // extraction's edge directions (vr_label_components; vr_components.hip).  The labels stay on the device
+    // (4 bytes a voxel, under `other`), the records come to the host, where the selection is made.  Unlike the mesh the labelling
+    // belongs to the voxels: loading, generating or smoothing a volume drops it; the layout, the window and the quirks do not (it
+    // keeps its own iso_s).  No volume: std::runtime_error; more than 2^32 - 2 components: a queued message and
+    // std::invalid_argument; an allocation that fails: DeviceMemoryError; a capped loop in a kernel: HipError; in each case the
+    // previous labelling stays.  No rendering state changes.
+    void labelComponents(int32_t iso, uint64_t *n_components);
+    bool hasComponents() const { return comp_valid_; }
+    void componentsInfo(int32_t *iso, uint64_t *n_components, uint64_t *n_inside, uint64_t *n_selected) const;
+    void readComponents(uint64_t *voxels, uint64_t *first_voxel, int32_t *bbox6, uint8_t *selected, uint64_t capacity) const;
+    void readLabels(uint32_t *labels, uint64_t n_voxels);
+    uint32_t componentAt(int i, int j, int k);
+    // selected: voxels >= min_voxels and, when keep_largest > 0, among the keep_largest first by (voxels descending, label ascending)
+    uint64_t selectComponents(uint64_t min_voxels, uint64_t keep_largest);
+    uint64_t selectComponentList(const uint32_t *labels, uint64_t n);   // exactly these; a label of 0 or above n_components: std::invalid_argument, nothing changes
+    // extractIsosurface at the labelling's iso value with INSIDE meaning "inside and its component selected": replaces the mesh
+    void extractComponents(uint64_t *n_vertices, uint64_t *n_triangles);
+    void freeComponents();
+    void setComponentIndexBits(int bits);    // aid for tests: 0 automatic (32 below 2^32 - 1 voxels, else 64), 32, 64
+    float lastComponentsMs() const { return last_comp_ms_; }   // HIP-event time of the last labelling's kernels
 
     int filter = 0, accum = 0, skip_empty = 0;
     int layout = 1;          // VR_LAYOUT_BRICKED: the faster HBM layout is the default (vr_set_layout)
@@ -191,6 +212,18 @@ private:
     DeviceBuffer<uint32_t> d_mesh_tri_;      // 3 indices a triangle
     float last_mesh_ms_ = 0.0f;
     uint64_t meshBytes() const;              // device bytes of the mesh
+    // the shared body of extractIsosurface and extractComponents; selected: launch_components_plane's bits or nullptr; ms: kernel time so far
+    void extractMesh(int32_t iso, float iso_s, const uint64_t *selected, float ms, uint64_t *n_vertices, uint64_t *n_triangles);
+    bool comp_valid_ = false;                // a labelling has succeeded (it may have no component) and was not dropped
+    int32_t comp_iso_ = 0;
+    float comp_iso_s_ = 0.0f;                // the iso value in stored units when the labelling was made
+    int comp_index_bits_ = 0;                // setComponentIndexBits
+    DeviceBuffer<uint32_t> d_labels_;        // one label per voxel, linear order
+    std::vector<uint64_t> comp_voxels_, comp_first_;   // the records, entry label - 1
+    std::vector<int32_t> comp_bbox_;         // 6 each
+    std::vector<uint8_t> comp_selected_;
+    uint64_t comp_inside_ = 0;
+    float last_comp_ms_ = 0.0f;
     hipError_t finishTimed(hipError_t e, float &ms);   // ends a stretch of kernels that began with ev0_ recorded, once `e` says they were all launched
     // geometry and voxel type of the volume that is RESIDENT (set only after a successful upload).
     // tex3D_dim / datasize_bytes above are GUI inputs of readVolumeData, like the reference's fields;

@@ -1,10 +1,13 @@
 // volume_ops.cpp -- RendererCore members that compute on the resident volume outside a frame: Gaussian smoothing
-// (vr_smooth_volume) and isosurface extraction with its mesh (vr_extract_isosurface; section 1.5).
+// (vr_smooth_volume), isosurface extraction with its mesh (vr_extract_isosurface; section 1.5) and the
+// connected components with the filtered extraction (vr_label_components, vr_extract_components; section 1.6).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <numeric>
 
 #include "renderer_core.h"
+#include "vr_components.h"
 #include "vr_mesh.h"
 #include "vr_smooth.h"
 
@@ -122,6 +125,7 @@ void RendererCore::smoothVolume(float sigma_x, float sigma_y, float sigma_z)
     else if (!d_loaded_) d_loaded_ = std::move(next);                    // (else `next` frees the earlier smoothing result)
     for (int a = 0; a < 3; a++) smooth_sigma_[a] = sigma[a];
     dropDerived();                                                       // what a load leaves behind for new voxels
+    freeComponents();                                                    // a labelling of the voxels rendered until now
 }
 
 // ---------------------------------------------------------------- extraction (vr_extract_isosurface)
@@ -142,11 +146,15 @@ void RendererCore::extractIsosurface(int32_t iso, uint64_t *n_vertices, uint64_t
 {
     requireDevice("extractIsosurface");
     if (!d_vol_) throw std::runtime_error("extractIsosurface: no dataset loaded");
+    extractMesh(iso, (float)((int64_t)iso + (datasize_bytes == 2 && (quirks & kQuirkU16Offset) ? 1000 : 0)), nullptr, 0.0f, n_vertices, n_triangles);   // isoStored's rule
+}
+
+void RendererCore::extractMesh(int32_t iso, float iso_s, const uint64_t *selected, float ms, uint64_t *n_vertices, uint64_t *n_triangles)
+{
     const int nx = res_dims_[0], ny = res_dims_[1], nz = res_dims_[2];
     uint64_t nv = 0, nt = 0;
     DeviceBuffer<float> pos, nrm;                        // the new mesh: moved into the handle at the very end
     DeviceBuffer<uint32_t> tri;
-    float ms = 0.0f;
     if (nx >= 2 && ny >= 2 && nz >= 2) {
         const uint64_t plane = (uint64_t)nx * (uint64_t)ny;
         uint64_t bound = mesh_workspace_limit;
@@ -172,7 +180,8 @@ void RendererCore::extractIsosurface(int32_t iso, uint64_t *n_vertices, uint64_t
         MeshSlab S = {};
         S.volume = d_vol_.get(); S.bytes_per_voxel = res_bytes_; S.layout = vol_layout_;
         S.nx = nx; S.ny = ny; S.nz = nz;
-        S.iso_s = (float)((int64_t)iso + (datasize_bytes == 2 && (quirks & kQuirkU16Offset) ? 1000 : 0));   // isoStored's rule
+        S.iso_s = iso_s;
+        S.selected = selected;
         for (int a = 0; a < 3; a++) S.spacing[a] = voxel_size[a];
         S.scan = d_scan; S.mask = mask.get();
         auto countAndScan = [&](int s) {
@@ -297,6 +306,195 @@ void RendererCore::saveMesh(const std::string &fn, const std::string &ext)
     }
     if (std::fclose(f) != 0) ok = false;
     if (!ok) throw IoError("saveMesh: writing " + fn + " failed");
+}
+
+// ---------------------------------------------------------------- components (vr_label_components)
+void RendererCore::freeComponents()
+{
+    d_labels_.reset();
+    comp_voxels_.clear(); comp_first_.clear(); comp_bbox_.clear(); comp_selected_.clear();
+    comp_inside_ = 0;
+    comp_valid_ = false;
+}
+
+void RendererCore::setComponentIndexBits(int bits)
+{
+    if (bits != 0 && bits != 32 && bits != 64) throw std::invalid_argument("setComponentIndexBits: 0, 32 or 64");
+    comp_index_bits_ = bits;
+}
+
+// Tile pass, seam pass, flatten, the scan of the root counts; then -- the number of components known -- the labels and the
+// records.  Everything new lives in locals until the very end: a call that throws leaves the previous labelling as it was.
+void RendererCore::labelComponents(int32_t iso, uint64_t *n_components)
+{
+    requireDevice("labelComponents");
+    if (!d_vol_) throw std::runtime_error("labelComponents: no dataset loaded");
+    ComponentsJob J = {};
+    J.volume = d_vol_.get(); J.bytes_per_voxel = res_bytes_; J.layout = vol_layout_;
+    J.nx = res_dims_[0]; J.ny = res_dims_[1]; J.nz = res_dims_[2];
+    J.iso_s = (float)((int64_t)iso + (datasize_bytes == 2 && (quirks & kQuirkU16Offset) ? 1000 : 0));   // isoStored's rule
+    const uint64_t nvox = component_voxels(J), words = component_words(J);
+    const bool fits32 = nvox < 0xffffffffull;
+    if (comp_index_bits_ == 32 && !fits32) throw std::invalid_argument("labelComponents: 32-bit parents cannot number this volume's voxels");
+    J.index_bits = comp_index_bits_ ? comp_index_bits_ : (fits32 ? 32 : 64);
+    DeviceBuffer<uint32_t> labels, error;
+    DeviceBuffer<uint64_t> parent64, bits, scan;
+    DeviceBuffer<uint8_t> temp;
+    const size_t temp_bytes = mesh_scan_temp_bytes(words + 1);
+    labels.allocOrNoMemory(nvox, "labelComponents: hipMalloc(labels)");
+    if (J.index_bits == 64) parent64.allocOrNoMemory(nvox, "labelComponents: hipMalloc(parents)");
+    bits.allocOrNoMemory(words, "labelComponents: hipMalloc(root bits)");
+    scan.allocOrNoMemory(words + 1, "labelComponents: hipMalloc(root counts)");
+    temp.allocOrNoMemory(temp_bytes ? temp_bytes : 16, "labelComponents: hipMalloc(scan scratch)");
+    error.allocOrNoMemory(1, "labelComponents: hipMalloc(error word)");
+    J.labels = labels.get();
+    J.parent = J.index_bits == 64 ? (void *)parent64.get() : (void *)labels.get();
+    J.bits = bits.get(); J.scan = scan.get(); J.error = error.get();
+    float ms = 0.0f;
+    hipError_t e = hipMemsetAsync(J.error, 0, sizeof(uint32_t), stream());
+    if (e == hipSuccess) e = hipEventRecord(ev0_, stream());
+    if (e == hipSuccess) e = launch_components_tiles(J, stream());
+    if (e == hipSuccess) e = launch_components_seams(J, stream());
+    if (e == hipSuccess) e = launch_components_flatten(J, stream());
+    if (e == hipSuccess) e = launch_mesh_scan(J.scan, words + 1, temp.get(), temp_bytes, stream());
+    check(finishTimed(e, ms), "component kernels (union-find)");
+    auto kernelsOk = [&] {
+        uint32_t flags = 0;
+        check(hipMemcpy(&flags, J.error, sizeof(flags), hipMemcpyDeviceToHost), "hipMemcpy(D2H error word)");
+        if (flags) throw HipError(hipErrorUnknown, "labelComponents: a union-find loop hit its iteration cap (flags " + std::to_string(flags) + ")");
+    };
+    kernelsOk();
+    uint64_t n = 0;
+    check(hipMemcpy(&n, J.scan + words, sizeof(n), hipMemcpyDeviceToHost), "hipMemcpy(D2H component count)");
+    if (n > 0xfffffffeull) {
+        setMessage("Error!", "The volume has " + std::to_string(n) + " connected components at this iso value: more than 32-bit labels number. "
+                                 "Smooth the volume or choose another iso value.");
+        throw std::invalid_argument("labelComponents: more than 2^32 - 2 components");
+    }
+    DeviceBuffer<uint64_t> voxels, first;
+    DeviceBuffer<int32_t> bbox;
+    std::vector<uint64_t> h_voxels((size_t)n), h_first((size_t)n);
+    std::vector<int32_t> h_bbox((size_t)n * 6);
+    if (n > 0) {
+        voxels.allocOrNoMemory(n, "labelComponents: hipMalloc(voxel counts)");
+        first.allocOrNoMemory(n, "labelComponents: hipMalloc(first voxels)");
+        bbox.allocOrNoMemory(n * 6, "labelComponents: hipMalloc(boxes)");
+        J.voxels = voxels.get(); J.first_voxel = first.get(); J.bbox = bbox.get();
+    }
+    e = hipEventRecord(ev0_, stream());
+    if (e == hipSuccess) e = launch_components_labels(J, n, stream());
+    if (e == hipSuccess && n > 0) e = launch_components_records(J, stream());
+    check(finishTimed(e, ms), "component kernels (labels)");
+    kernelsOk();
+    if (n > 0) {
+        check(hipMemcpy(h_voxels.data(), J.voxels, n * sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy(D2H voxel counts)");
+        check(hipMemcpy(h_first.data(), J.first_voxel, n * sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy(D2H first voxels)");
+        check(hipMemcpy(h_bbox.data(), J.bbox, n * 6 * sizeof(int32_t), hipMemcpyDeviceToHost), "hipMemcpy(D2H boxes)");
+    }
+    std::vector<uint8_t> h_selected((size_t)n, 1);
+    d_labels_ = std::move(labels);
+    comp_voxels_ = std::move(h_voxels); comp_first_ = std::move(h_first); comp_bbox_ = std::move(h_bbox); comp_selected_ = std::move(h_selected);
+    comp_inside_ = std::accumulate(comp_voxels_.begin(), comp_voxels_.end(), (uint64_t)0);
+    comp_iso_ = iso; comp_iso_s_ = J.iso_s; comp_valid_ = true;
+    last_comp_ms_ = ms;
+    if (n_components) *n_components = n;
+}
+
+void RendererCore::componentsInfo(int32_t *iso, uint64_t *n_components, uint64_t *n_inside, uint64_t *n_selected) const
+{
+    if (!comp_valid_) throw std::invalid_argument("componentsInfo: no components have been labelled");
+    if (iso) *iso = comp_iso_;
+    if (n_components) *n_components = comp_voxels_.size();
+    if (n_inside) *n_inside = comp_inside_;
+    if (n_selected) *n_selected = (uint64_t)std::count(comp_selected_.begin(), comp_selected_.end(), (uint8_t)1);
+}
+
+void RendererCore::readComponents(uint64_t *voxels, uint64_t *first_voxel, int32_t *bbox6, uint8_t *selected, uint64_t capacity) const
+{
+    if (!comp_valid_) throw std::invalid_argument("readComponents: no components have been labelled");
+    const size_t n = comp_voxels_.size();
+    if ((voxels || first_voxel || bbox6 || selected) && capacity < n) throw std::invalid_argument("readComponents: buffer too small");
+    if (voxels) std::copy(comp_voxels_.begin(), comp_voxels_.end(), voxels);
+    if (first_voxel) std::copy(comp_first_.begin(), comp_first_.end(), first_voxel);
+    if (bbox6) std::copy(comp_bbox_.begin(), comp_bbox_.end(), bbox6);
+    if (selected) std::copy(comp_selected_.begin(), comp_selected_.end(), selected);
+}
+
+void RendererCore::readLabels(uint32_t *labels, uint64_t n_voxels)
+{
+    if (!comp_valid_) throw std::invalid_argument("readLabels: no components have been labelled");
+    if (!labels || n_voxels < d_labels_.size()) throw std::invalid_argument("readLabels: buffer too small");
+    requireDevice("readLabels");
+    check(hipMemcpyAsync(labels, d_labels_.get(), d_labels_.bytes(), hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H labels)");
+    check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
+}
+
+uint32_t RendererCore::componentAt(int i, int j, int k)
+{
+    if (!comp_valid_) throw std::invalid_argument("componentAt: no components have been labelled");
+    if (i < 0 || j < 0 || k < 0 || i >= res_dims_[0] || j >= res_dims_[1] || k >= res_dims_[2]) throw std::invalid_argument("componentAt: the voxel lies outside the volume");
+    requireDevice("componentAt");
+    uint32_t label = 0;
+    const uint64_t at = (uint64_t)i + (uint64_t)res_dims_[0] * ((uint64_t)j + (uint64_t)res_dims_[1] * (uint64_t)k);
+    check(hipMemcpyAsync(&label, d_labels_.get() + at, sizeof(label), hipMemcpyDeviceToHost, stream()), "hipMemcpy(D2H label)");
+    check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
+    return label;
+}
+
+uint64_t RendererCore::selectComponents(uint64_t min_voxels, uint64_t keep_largest)
+{
+    if (!comp_valid_) throw std::invalid_argument("selectComponents: no components have been labelled");
+    const size_t n = comp_voxels_.size();
+    std::vector<uint8_t> sel(n, 0);
+    if (keep_largest == 0 || keep_largest >= n) {
+        for (size_t c = 0; c < n; c++) sel[c] = comp_voxels_[c] >= min_voxels;
+    } else {
+        std::vector<uint32_t> order(n);
+        std::iota(order.begin(), order.end(), 0u);
+        auto before = [&](uint32_t a, uint32_t b) { return comp_voxels_[a] != comp_voxels_[b] ? comp_voxels_[a] > comp_voxels_[b] : a < b; };
+        std::partial_sort(order.begin(), order.begin() + (size_t)keep_largest, order.end(), before);
+        for (size_t q = 0; q < (size_t)keep_largest; q++) sel[order[q]] = comp_voxels_[order[q]] >= min_voxels;
+    }
+    comp_selected_ = std::move(sel);
+    return (uint64_t)std::count(comp_selected_.begin(), comp_selected_.end(), (uint8_t)1);
+}
+
+uint64_t RendererCore::selectComponentList(const uint32_t *labels, uint64_t n)
+{
+    if (!comp_valid_) throw std::invalid_argument("selectComponentList: no components have been labelled");
+    if (!labels && n > 0) throw std::invalid_argument("selectComponentList: null list");
+    for (uint64_t q = 0; q < n; q++)
+        if (labels[q] == 0 || labels[q] > comp_voxels_.size()) throw std::invalid_argument("selectComponentList: label " + std::to_string(labels[q]) + " does not exist");
+    std::vector<uint8_t> sel(comp_voxels_.size(), 0);
+    for (uint64_t q = 0; q < n; q++) sel[labels[q] - 1u] = 1;
+    comp_selected_ = std::move(sel);
+    return (uint64_t)std::count(comp_selected_.begin(), comp_selected_.end(), (uint8_t)1);
+}
+
+// The selection as one bit per voxel (a small kernel over the labels), then extractIsosurface's body with that plane as INSIDE
+void RendererCore::extractComponents(uint64_t *n_vertices, uint64_t *n_triangles)
+{
+    requireDevice("extractComponents");
+    if (!comp_valid_) throw std::invalid_argument("extractComponents: no components have been labelled");
+    if (!d_vol_) throw std::runtime_error("extractComponents: no dataset loaded");
+    const uint64_t nvox = d_labels_.size(), words = (nvox + 63) / 64;
+    DeviceBuffer<uint64_t> plane;
+    DeviceBuffer<uint8_t> selected;
+    plane.allocOrNoMemory(words, "extractComponents: hipMalloc(selection plane)");
+    float ms = 0.0f;
+    hipError_t e = hipSuccess;
+    if (comp_selected_.empty()) {
+        e = hipMemsetAsync(plane.get(), 0, plane.bytes(), stream());
+        if (e == hipSuccess) e = hipStreamSynchronize(stream());
+        check(e, "hipMemset(selection plane)");
+    } else {
+        selected.allocOrNoMemory(comp_selected_.size(), "extractComponents: hipMalloc(selection)");
+        e = hipMemcpyAsync(selected.get(), comp_selected_.data(), comp_selected_.size(), hipMemcpyHostToDevice, stream());
+        if (e == hipSuccess) e = hipEventRecord(ev0_, stream());
+        if (e == hipSuccess) e = launch_components_plane(d_labels_.get(), selected.get(), nvox, plane.get(), stream());
+        check(finishTimed(e, ms), "selection kernel");
+    }
+    extractMesh(comp_iso_, comp_iso_s_, plane.get(), ms, n_vertices, n_triangles);
 }
 
 }  // namespace vr

@@ -429,6 +429,72 @@ int vr_get_mesh_ms(vr_handle h, float *ms)
     return VR_OK;
 }
 
+int vr_label_components(vr_handle h, int32_t iso_value, uint64_t *n_components)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.labelComponents(iso_value, n_components); });
+}
+
+int vr_get_components_info(vr_handle h, int32_t *iso_value, uint64_t *n_components, uint64_t *n_inside, uint64_t *n_selected)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.componentsInfo(iso_value, n_components, n_inside, n_selected); });
+}
+
+int vr_read_components(vr_handle h, uint64_t *voxels, uint64_t *first_voxel, int32_t *bbox6, uint8_t *selected, uint64_t capacity)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.readComponents(voxels, first_voxel, bbox6, selected, capacity); });
+}
+
+int vr_read_labels(vr_handle h, uint32_t *labels, uint64_t n_voxels)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.readLabels(labels, n_voxels); });
+}
+
+int vr_component_at(vr_handle h, int i, int j, int k, uint32_t *label)
+{
+    return guarded(h, [&](vr::RendererCore &c) {
+        if (!label) throw std::invalid_argument("vr_component_at: null argument");
+        *label = c.componentAt(i, j, k);
+    });
+}
+
+int vr_select_components(vr_handle h, uint64_t min_voxels, uint64_t keep_largest, uint64_t *n_selected)
+{
+    return guarded(h, [&](vr::RendererCore &c) {
+        const uint64_t n = c.selectComponents(min_voxels, keep_largest);
+        if (n_selected) *n_selected = n;
+    });
+}
+
+int vr_select_component_list(vr_handle h, const uint32_t *labels, uint64_t n, uint64_t *n_selected)
+{
+    return guarded(h, [&](vr::RendererCore &c) {
+        const uint64_t got = c.selectComponentList(labels, n);
+        if (n_selected) *n_selected = got;
+    });
+}
+
+int vr_extract_components(vr_handle h, uint64_t *n_vertices, uint64_t *n_triangles)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.extractComponents(n_vertices, n_triangles); });
+}
+
+int vr_free_components(vr_handle h)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.freeComponents(); });
+}
+
+int vr_set_component_index_bits(vr_handle h, int bits)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.setComponentIndexBits(bits); });
+}
+
+int vr_get_components_ms(vr_handle h, float *ms)
+{
+    if (!h || !ms) return VR_E_INVALID;
+    *ms = h->core.lastComponentsMs();
+    return VR_OK;
+}
+
 int vr_set_autotune(vr_handle h, int enable)
 {
     if (!h) return VR_E_INVALID;

@@ -27,6 +27,9 @@ struct MeshSlab {
     float *positions, *normals;
     uint32_t *triangles;
     uint64_t vertex_base, triangle_base;
+    // vr_extract_components: one bit per voxel of the WHOLE volume in linear order (launch_components_plane), which replaces
+    // s >= iso_s as the definition's INSIDE; NULL: the plain comparison
+    const uint64_t *selected;
 };
 
 constexpr uint64_t kMeshMaxSlabVoxels = 1ull << 28;      // 12 triangles a cell: every partial sum stays below 2^32

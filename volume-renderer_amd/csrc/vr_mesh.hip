@@ -113,6 +113,7 @@ struct MeshArgs {
     float *pos, *nrm;
     uint32_t *tri;
     uint32_t vbase, tbase;
+    const uint64_t *selected;                            // SelectedInside only: one bit per voxel in linear order
 };
 
 __device__ __forceinline__ uint64_t voxel_index(const MeshArgs &A, uint32_t i, uint32_t j, uint32_t k)
@@ -144,6 +145,33 @@ __device__ __forceinline__ void load_corners(const MeshArgs &A, uint32_t i, uint
     }
 }
 
+// Step 2's INSIDE as a template parameter of the two kernels that evaluate it.  PlainInside: s >= iso_s (vr_extract_isosurface).
+// SelectedInside: the voxel's bit in the plane that launch_components_plane wrote -- inside at the labelling's iso value AND its
+// component selected (vr_extract_components).  in8: the bits of the cell's eight corners as load_corners reads them.
+struct PlainInside {
+    static __device__ __forceinline__ uint32_t in8(const MeshArgs &A, uint32_t, uint32_t, uint32_t, const float s[8])
+    {
+        uint32_t bits = 0;
+#pragma unroll
+        for (int c = 0; c < 8; c++) bits |= (uint32_t)(s[c] >= A.iso_s) << c;
+        return bits;
+    }
+};
+
+struct SelectedInside {
+    static __device__ __forceinline__ uint32_t in8(const MeshArgs &A, uint32_t i, uint32_t j, uint32_t k, const float[8])
+    {
+        const uint32_t hx = i + 1 < A.nx, hy = j + 1 < A.ny, hz = k + 1 < A.nz;
+        uint32_t bits = 0;
+#pragma unroll
+        for (uint32_t c = 0; c < 8; c++) {
+            const uint64_t v = (uint64_t)(i + ((c & 1) & hx)) + (uint64_t)A.nx * ((uint64_t)(j + ((c >> 1 & 1) & hy)) + (uint64_t)A.ny * (uint64_t)(k + ((c >> 2 & 1) & hz)));
+            bits |= (uint32_t)(A.selected[v >> 6] >> (v & 63u) & 1u) << c;
+        }
+        return bits;
+    }
+};
+
 __device__ __forceinline__ uint32_t corner_of_dir(int d)   // e_d as corner bits
 {
     constexpr uint32_t bits = 1u | 2u << 3 | 4u << 6 | 3u << 9 | 5u << 12 | 6u << 15 | 7u << 18;
@@ -170,7 +198,7 @@ __device__ __forceinline__ void decode(const MeshArgs &A, uint32_t g, uint32_t &
 }
 
 // ------------------------------------------------------------------ count
-template <typename VoxelT>
+template <typename VoxelT, typename Inside>
 __global__ __launch_bounds__(256) void mesh_count_kernel(const MeshArgs A)
 {
     const uint32_t n = A.nx * A.ny * (uint32_t)(A.zs - A.z0);
@@ -182,9 +210,7 @@ __global__ __launch_bounds__(256) void mesh_count_kernel(const MeshArgs A)
     float s[8];
     uint32_t exists;
     load_corners<VoxelT>(A, i, j, k, s, exists);
-    uint32_t in8 = 0;
-#pragma unroll
-    for (int c = 0; c < 8; c++) in8 |= (uint32_t)(s[c] >= A.iso_s) << c;
+    const uint32_t in8 = Inside::in8(A, i, j, k, s);
     // direction d leads to corner corner_of_dir(d): a vertex where that voxel exists and lies on the other side
     const uint32_t differs = (in8 ^ (0u - (in8 & 1u))) & exists & 0xfeu;
     uint32_t mk = 0;
@@ -212,7 +238,7 @@ __device__ __forceinline__ void gradient(const MeshArgs &A, uint32_t i, uint32_t
     g[2] = load_s<VoxelT>(A, i, j, min(k + 1, A.nz - 1)) - load_s<VoxelT>(A, i, j, k > 0 ? k - 1 : 0);
 }
 
-template <typename VoxelT>
+template <typename VoxelT, typename Inside>
 __global__ __launch_bounds__(256) void mesh_emit_kernel(const MeshArgs A)
 {
     const uint32_t plane = A.nx * A.ny;
@@ -262,9 +288,7 @@ __global__ __launch_bounds__(256) void mesh_emit_kernel(const MeshArgs A)
     }
 
     if (ntri != 0) {
-        uint32_t in8 = 0;
-#pragma unroll
-        for (int c = 0; c < 8; c++) in8 |= (uint32_t)(s[c] >= A.iso_s) << c;
+        const uint32_t in8 = Inside::in8(A, i, j, k, s);
         // first vertex and active directions of the seven voxels that own the cell's edges (corner 7 owns none of them)
         uint32_t first[7], act[7];
 #pragma unroll
@@ -289,8 +313,8 @@ __global__ __launch_bounds__(256) void mesh_emit_kernel(const MeshArgs A)
     }
 }
 
-template <typename VoxelT>
-hipError_t launch_mesh_type(const MeshSlab &S, bool emit, hipStream_t st)
+template <typename VoxelT, typename Inside>
+hipError_t launch_mesh_pred(const MeshSlab &S, bool emit, hipStream_t st)
 {
     MeshArgs A = {};
     A.vol = S.volume;
@@ -302,15 +326,22 @@ hipError_t launch_mesh_type(const MeshSlab &S, bool emit, hipStream_t st)
     A.scan = S.scan; A.mask = S.mask;
     A.pos = S.positions; A.nrm = S.normals; A.tri = S.triangles;
     A.vbase = (uint32_t)S.vertex_base; A.tbase = (uint32_t)S.triangle_base;
+    A.selected = S.selected;
     const uint64_t plane = (uint64_t)S.nx * (uint64_t)S.ny;
     if (!emit) {
         const uint64_t threads = plane * (uint64_t)(A.zs - A.z0) + 1;
-        hipLaunchKernelGGL((mesh_count_kernel<VoxelT>), dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, st, A);
+        hipLaunchKernelGGL((mesh_count_kernel<VoxelT, Inside>), dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, st, A);
     } else {
         const uint64_t threads = plane * (uint64_t)(A.z1 - A.z0);
-        hipLaunchKernelGGL((mesh_emit_kernel<VoxelT>), dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, st, A);
+        hipLaunchKernelGGL((mesh_emit_kernel<VoxelT, Inside>), dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, st, A);
     }
     return hipGetLastError();
+}
+
+template <typename VoxelT>
+hipError_t launch_mesh_type(const MeshSlab &S, bool emit, hipStream_t st)
+{
+    return S.selected ? launch_mesh_pred<VoxelT, SelectedInside>(S, emit, st) : launch_mesh_pred<VoxelT, PlainInside>(S, emit, st);
 }
 
 }  // namespace

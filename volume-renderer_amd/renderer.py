@@ -137,6 +137,17 @@ def load_library() -> C.CDLL:
         "vr_free_mesh": (i32, [h]),
         "vr_set_mesh_workspace": (i32, [h, C.c_uint64]),
         "vr_get_mesh_ms": (i32, [h, C.POINTER(f32)]),
+        "vr_label_components": (i32, [h, i32, C.POINTER(C.c_uint64)]),
+        "vr_get_components_info": (i32, [h, C.POINTER(i32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "vr_read_components": (i32, [h, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_uint64]),
+        "vr_read_labels": (i32, [h, C.POINTER(C.c_uint32), C.c_uint64]),
+        "vr_component_at": (i32, [h, i32, i32, i32, C.POINTER(C.c_uint32)]),
+        "vr_select_components": (i32, [h, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "vr_select_component_list": (i32, [h, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64)]),
+        "vr_extract_components": (i32, [h, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "vr_free_components": (i32, [h]),
+        "vr_set_component_index_bits": (i32, [h, i32]),
+        "vr_get_components_ms": (i32, [h, C.POINTER(f32)]),
         "vr_set_autotune": (i32, [h, i32]),
         "vr_export_choices": (i32, [h, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
         "vr_import_choices": (i32, [h, C.c_void_p, C.c_size_t, C.POINTER(i32)]),
@@ -700,6 +711,75 @@ class RendererCore:
         """HIP-event time of the last extractIsosurface's kernels, ms"""
         ms = C.c_float(0.0)
         self._check(self._lib.vr_get_mesh_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def labelComponents(self, iso) -> int:
+        """vr_label_components: the connected components of the voxels s >= iso of the volume being rendered (14-neighbourhood of
+        the extraction's edge directions), labelled on the device; every component starts selected.  Returns their number."""
+        n = C.c_uint64(0)
+        self._check(self._lib.vr_label_components(self._h, int(iso), C.byref(n)))
+        return int(n.value)
+
+    def componentsInfo(self) -> dict:
+        """the resident labelling: dict(iso, components, inside, selected)"""
+        iso, n, inside, sel = C.c_int32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.vr_get_components_info(self._h, C.byref(iso), C.byref(n), C.byref(inside), C.byref(sel)))
+        return dict(iso=int(iso.value), components=int(n.value), inside=int(inside.value), selected=int(sel.value))
+
+    def readComponents(self) -> dict:
+        """the records, entry label - 1: voxels [n] uint64, first_voxel [n] uint64 (linear index), bbox [n, 6] int32 (lo x, y, z,
+        hi x, y, z, inclusive), selected [n] bool"""
+        n = self.componentsInfo()["components"]
+        voxels, first = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        bbox, sel = np.zeros((n, 6), dtype=np.int32), np.zeros(n, dtype=np.uint8)
+        self._check(self._lib.vr_read_components(self._h, voxels.ctypes.data_as(C.POINTER(C.c_uint64)), first.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 bbox.ctypes.data_as(C.POINTER(C.c_int32)), sel.ctypes.data_as(C.POINTER(C.c_uint8)), n))
+        return dict(voxels=voxels, first_voxel=first, bbox=bbox, selected=sel.astype(bool))
+
+    def readLabels(self) -> np.ndarray:
+        """the labels [nz, ny, nx] uint32: 0 outside, else the component's number"""
+        nx, ny, nz = self.dims[0]
+        out = np.zeros((nz, ny, nx), dtype=np.uint32)
+        self._check(self._lib.vr_read_labels(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size))
+        return out
+
+    def componentAt(self, i, j, k) -> int:
+        label = C.c_uint32(0)
+        self._check(self._lib.vr_component_at(self._h, int(i), int(j), int(k), C.byref(label)))
+        return int(label.value)
+
+    def selectComponents(self, min_voxels=0, keep_largest=0) -> int:
+        """vr_select_components: voxels >= min_voxels and, when keep_largest > 0, among the keep_largest first by (voxels
+        descending, label ascending).  Returns the number selected."""
+        n = C.c_uint64(0)
+        self._check(self._lib.vr_select_components(self._h, C.c_uint64(int(min_voxels)), C.c_uint64(int(keep_largest)), C.byref(n)))
+        return int(n.value)
+
+    def selectComponentList(self, labels) -> int:
+        """vr_select_component_list: exactly these labels.  Returns the number selected."""
+        a = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+        n = C.c_uint64(0)
+        self._check(self._lib.vr_select_component_list(self._h, a.ctypes.data_as(C.POINTER(C.c_uint32)), a.size, C.byref(n)))
+        return int(n.value)
+
+    def extractComponents(self):
+        """vr_extract_components: the isosurface of the selected components only, at the labelling's iso value; replaces the
+        resident mesh (meshInfo, readMesh, saveMesh).  Returns (vertices, triangles)."""
+        nv, nt = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.vr_extract_components(self._h, C.byref(nv), C.byref(nt)))
+        return int(nv.value), int(nt.value)
+
+    def freeComponents(self):
+        self._check(self._lib.vr_free_components(self._h))
+
+    def setComponentIndexBits(self, bits):
+        """aid for tests: the width of the union-find parents of the next labelling: 0 automatic, 32, 64"""
+        self._check(self._lib.vr_set_component_index_bits(self._h, int(bits)))
+
+    def componentsMs(self) -> float:
+        """HIP-event time of the last labelComponents' kernels, ms"""
+        ms = C.c_float(0.0)
+        self._check(self._lib.vr_get_components_ms(self._h, C.byref(ms)))
         return float(ms.value)
 
     def setKernelVariant(self, variant):
