@@ -1,7 +1,7 @@
 // launch_tuner.h -- the measured work model of kernel variant 0 (vr_set_autotune): which of a configuration's candidate
 // kernels a launch runs.  Host-only and HIP-free: a state machine over a key, a candidate list and millisecond timings.
-// RendererCore enumerates the candidates, owns the events that time them and feeds the results in (renderer_core.cpp:
-// tuneChoose, tuneCollect).
+// launch_plan.h enumerates the candidates; RendererCore owns the events that time them and feeds the results in
+// (renderer_core.cpp: tuneChoose, tuneCollect).
 //
 // Every candidate kernel of a configuration renders the same bits, so the first frames of a configuration double as
 // measurements -- each candidate is timed a few times, the fastest is kept until the configuration changes.

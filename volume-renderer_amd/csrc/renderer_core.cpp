@@ -13,6 +13,7 @@
 #include <fstream>
 #include <iostream>
 
+#include "launch_plan.h"
 #include "tile_schedule.h"
 #include "volume_io.h"
 #include "vr_iso.h"
@@ -204,7 +205,7 @@ void RendererCore::freeVolume()
 
 void RendererCore::dropDerived()
 {
-    if (tile_table_skip_sig_ != 0) tile_table_skip_sig_ = -1;            // (an order built on the old volume's visibility)
+    tiles_.invalidateSkipOrder();                                        // (an order built on the old volume's visibility)
     copies_.dropAll();
 }
 
@@ -602,7 +603,8 @@ void RendererCore::buildFrame(FrameParams &P, LaunchConfig &L)
     const float num = std::sqrt((e2 * e2 + e1 * e1) + e0 * e0);
     const float fx = (float)nx, fy = (float)ny, fz = (float)nz;
     // (the isosurface mode marches the composite mode's positions, whatever the MIP switch says)
-    const float den = (u_.is_MIP == 1 && !iso_enable_) ? std::sqrt((fz * fz + fy * fy) + fx * fx) : std::sqrt((fy * fy + fz * fz) + fx * fx);
+    const bool iso = frameMode() == FrameMode::Isosurface;
+    const float den = (u_.is_MIP == 1 && !iso) ? std::sqrt((fz * fz + fy * fy) + fx * fx) : std::sqrt((fy * fy + fz * fz) + fx * fx);
     P.step = num / den;
     P.alpha_scale = u_.alpha_scale;
     P.min_val = u_.min_val; P.max_val = u_.max_val;
@@ -617,10 +619,10 @@ void RendererCore::buildFrame(FrameParams &P, LaunchConfig &L)
 
     L.bytes_per_voxel = res_bytes_;
     L.filter = filter;
-    L.mip = iso_enable_ ? 0 : u_.is_MIP;
+    L.mip = iso ? 0 : u_.is_MIP;
     L.layout = vol_layout_;
     L.generic = force_generic == 1 ? 1 : 0;
-    // kernel variants 6 .. 11: TRILINEAR on the LDS-staged kernel wherever it is eligible, in one of its shapes (0: see refreshTileSchedule)
+    // kernel variants 6 .. 11: TRILINEAR on the LDS-staged kernel wherever it is eligible, in one of its shapes (0: see launch_plan.h, firstGuess)
     L.tri_slab = (force_generic >= 6 && force_generic <= 11) ? force_generic - 5 : 0;
     L.pipelined = 0;
     L.short_batches = 0;
@@ -670,14 +672,17 @@ void RendererCore::setFramebufferFormat(int fmt)
 // an isosurface frame is RGBA: a (grey, alpha) target is refused -- before the device checks, it is a configuration error
 void RendererCore::refuseIsoGreyAlpha() const
 {
-    if (iso_enable_ && fb_format_ == 1 && ext_fb_)
+    if (frameMode() == FrameMode::Isosurface && fb_format_ == 1 && ext_fb_)
         throw std::invalid_argument("render: the (grey, alpha) target format needs a grey mode (the isosurface mode is not one)");
 }
 
-// the skip grid's cells (8x8x8 voxels) per axis of the resident volume
+// the skip grid's cells per axis of the resident volume (after ensureSkipGrid() has passed: no limit check here)
 void RendererCore::setSkipCells(FrameParams &P) const
 {
-    P.cnx = (int32_t)((res_dims_[0] + 7) / 8); P.cny = (int32_t)((res_dims_[1] + 7) / 8); P.cnz = (int32_t)((res_dims_[2] + 7) / 8);
+    uint32_t c[3];
+    size_t cells;
+    (void)skipGridCells(res_dims_[0], res_dims_[1], res_dims_[2], c, cells);
+    P.cnx = (int32_t)c[0]; P.cny = (int32_t)c[1]; P.cnz = (int32_t)c[2];
 }
 
 // a per-pixel float target beside the colour one (depth, values): grown to this frame's rows x width; a new allocation is filled
@@ -690,72 +695,63 @@ void RendererCore::growFloatTarget(DeviceBuffer<float> &d, int fill, const char 
     check(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d.get()), fill, n, stream()), (std::string("hipMemset(") + name + ")").c_str());
 }
 
-float4 *RendererCore::prepareLaunch(FrameParams &P, LaunchConfig &L)
+RendererCore::PreparedLaunch RendererCore::prepareLaunch()
 {
     refuseIsoGreyAlpha();
     requireDevice("render");
     if (!cs_program_) throw std::runtime_error("render: no shader loaded (call loadShader first)");
     if (!d_vol_) throw std::runtime_error("render: no dataset loaded");
-    float4 *fb = ext_fb_ ? reinterpret_cast<float4 *>(ext_fb_) : d_fb_.get();
-    if (!fb) throw std::runtime_error("render: setup() has not allocated the framebuffer");
+    PreparedLaunch F;
+    FrameParams &P = F.P;
+    LaunchConfig &L = F.L;
+    F.fb = ext_fb_ ? reinterpret_cast<float4 *>(ext_fb_) : d_fb_.get();
+    if (!F.fb) throw std::runtime_error("render: setup() has not allocated the framebuffer");
     if (fb_format_ == 1 && ext_fb_ && !tf_lut_.empty())
         throw std::invalid_argument("render: the (grey, alpha) target format needs a grey mode (no transfer function)");
-    if (iso_enable_) {
-        // the isosurface kernel (vr_iso.hip): one kernel, no measured choice, no tile table or speed copies; the skip grid when
-        // skipping is on and some cell lies below the iso value
-        refuseIsoGreyAlpha();
-        buildFrame(P, L);
-        P.skip_empty = 0;
-        iso_skip_grid_ = nullptr;
-        if (skip_empty && ensureSkipGrid() && (float)copies_.skipGridMin() < isoStored()) {
-            setSkipCells(P);
-            iso_skip_grid_ = copies_.skipGrid();
-        }
-        growFloatTarget(d_depth_, 0x7f800000, "depth");   // +inf
-        depth_rows_ = (ext_fb_ && fb_compact_) ? localRows() : framebuffer_size[1];
-        depth_w_ = framebuffer_size[0];
-        noMeasuredChoice();
-        return fb;
-    }
-    if (reslice_enable_) {
-        // the reslice kernel (vr_reslice.hip): one kernel, no measured choice (nothing explored, settled or evicted), no tile
-        // table, speed copies or skip grid
-        buildFrame(P, L);
-        P.skip_empty = 0;
-        growFloatTarget(d_values_, 0x7fc00000, "values");   // quiet NaN
-        values_rows_ = (ext_fb_ && fb_compact_) ? localRows() : framebuffer_size[1];
-        values_w_ = framebuffer_size[0];
-        noMeasuredChoice();
-        return fb;
-    }
-    if (shadeFrame()) {
-        // the gradient-lit composite kernel (vr_shade.hip): one kernel, no measured choice (nothing explored, settled or evicted),
-        // no tile table or speed copies; the skip grid when skipping is on and some cell classifies to alpha 0 (the composite
-        // mode's threshold rule: NEAREST per value, TRILINEAR the table's whole leading zero-alpha run)
-        buildFrame(P, L);
-        P.skip_empty = 0;
-        shade_skip_grid_ = nullptr;
-        int thresh = 0;
-        if (skip_empty && zeroAlphaThreshold(P, filter == 1, thresh) && ensureSkipGrid() && thresh >= (int)copies_.skipGridMin()) {
-            setSkipCells(P);
-            shade_skip_grid_ = copies_.skipGrid();
-            shade_skip_thresh_ = thresh;
-        }
-        noMeasuredChoice();
-        return fb;
-    }
-    if (filter == 1) warmTrilinear();          // (a caller that set the public field directly; a no-op once done)
+    F.mode = frameMode();
+    if (F.mode == FrameMode::RayMarch && filter == 1) warmTrilinear();   // (a caller that set the public field directly; a no-op once done)
     buildFrame(P, L);
+    if (F.mode != FrameMode::RayMarch) {
+        // the isosurface, reslice and gradient-lit composite kernels (vr_iso.hip, vr_reslice.hip, vr_shade.hip): one kernel each, no
+        // measured choice (nothing explored, settled or evicted), no tile table or speed copies
+        P.skip_empty = 0;
+        int thresh = 0;
+        const float *tf = tf_lut_.empty() ? nullptr : tf_lut_.data();
+        if (F.mode == FrameMode::Isosurface) {
+            // the skip grid when skipping is on and some cell lies below the iso value
+            if (skip_empty && ensureSkipGrid() && (float)copies_.skipGridMin() < isoStored()) F.skip_grid = copies_.skipGrid();
+            growFloatTarget(d_depth_, 0x7f800000, "depth");   // +inf
+            depth_rows_ = (ext_fb_ && fb_compact_) ? localRows() : framebuffer_size[1];
+            depth_w_ = framebuffer_size[0];
+        } else if (F.mode == FrameMode::Reslice) {
+            growFloatTarget(d_values_, 0x7fc00000, "values");   // quiet NaN
+            values_rows_ = (ext_fb_ && fb_compact_) ? localRows() : framebuffer_size[1];
+            values_w_ = framebuffer_size[0];
+        } else if (skip_empty && zeroAlphaThreshold(P, u_.min_val, u_.max_val, tf, filter == 1, thresh) && ensureSkipGrid() && thresh >= (int)copies_.skipGridMin()) {
+            // shaded: the skip grid when skipping is on and some cell classifies to alpha 0 (the composite mode's threshold rule:
+            // NEAREST per value, TRILINEAR the table's whole leading zero-alpha run)
+            F.skip_grid = copies_.skipGrid();
+            F.skip_thresh = thresh;
+        }
+        if (F.skip_grid) setSkipCells(P);
+        noMeasuredChoice();
+        return F;
+    }
     refreshSkipGrid(P, L);
-    refreshTileSchedule(P, L);
+    // the tile tables, then the first guess of a launch that walks one
+    const TileTableNeeds needs = tileTableNeeds(P, L, force_generic);
+    const int rows = launch_local_rows(P);
+    if (tile_order && needs.any && rows > 0) {
+        tiles_.refresh(P, L, rows, needs.tall, needs.small, needs.skip_order ? L.skip_grid : nullptr, exact_max_, stream());
+        firstGuess(P, L, force_generic, tiles_.active(), tiles_.longest());
+    }
     refreshPacked12(P, L);
     refreshApron(P, L);
-    // (the half-layer shapes need the per-axis copies: without them -- allocation failed -- the round-3 choice)
-    if ((L.tri_slab == 3 || L.tri_slab == 4) && (L.apron_y == nullptr || L.apron_x == nullptr) && force_generic == 0) L.tri_slab = tri_path_candidate(P, L) ? 0 : 1;
+    halfLayerFallback(P, L, force_generic);
     // the specialised kernels gather from the packed copy when their address tables fit (vr_kernels.hip: dispatch_fast3)
     last_packed12_bytes_ = (L.packed12 && P.nx + P.ny + P.nz <= 3072) ? (size_t)L.packed12_bytes : 0;
-    tuneChoose(P, L);
-    return fb;
+    tuneChoose(F);
+    return F;
 }
 
 // the LDS-staged TRILINEAR kernel's seven code objects (vr_tslab.hip), loaded when TRILINEAR is selected -- vr_set_filter,
@@ -770,30 +766,33 @@ void RendererCore::warmTrilinear()
     tslab_warm_ = true;
 }
 
-void RendererCore::launch(uint32_t *spp)
+// one frame: prepare, launch, and where the launch is a measurement of the work model hand its time to the tuner.  The
+// reference brackets glDispatchCompute with a GL_TIME_ELAPSED query and blocks on its result (src/RendererCore.cpp:149-153):
+// `blocking` is that shape with HIP events (the dispatch only: all host-side preparation happens first), and measures whatever
+// the tuner asks for.  Otherwise a measurement takes a TuneSlot while one is free -- events read later without blocking
+// (tuneCollect) -- and a countSamples launch never measures
+void RendererCore::launch(uint32_t *spp, bool blocking)
 {
-    FrameParams P;
-    LaunchConfig L;
-    float4 *fb = prepareLaunch(P, L);
-    // a measurement launch of the work model: events around the kernel, read later without blocking (tuneCollect)
-    const LaunchTuner::Pick pick = tune_pick_;
-    tune_pick_ = {};
-    const bool measure = pick.measure && spp == nullptr && tune_count_ < kTuneSlots;
+    const PreparedLaunch F = prepareLaunch();
+    const LaunchTuner::Pick &pick = F.pick;
+    const bool measure = pick.measure && spp == nullptr && (blocking || tune_count_ < kTuneSlots);
     TuneSlot &slot = tune_slot_[(tune_head_ + tune_count_) % kTuneSlots];
-    if (measure) check(hipEventRecord(slot.ev0, stream()), "hipEventRecord");
-    check(launchKernel(P, L, fb, spp), "raymarch launch");
-    if (measure) {
-        check(hipEventRecord(slot.ev1, stream()), "hipEventRecord");
+    const hipEvent_t e0 = blocking ? ev0_ : slot.ev0, e1 = blocking ? ev1_ : slot.ev1;
+    if (blocking || measure) check(hipEventRecord(e0, stream()), "hipEventRecord");
+    check(launchKernel(F, spp), "raymarch launch");
+    if (blocking || measure) check(hipEventRecord(e1, stream()), "hipEventRecord");
+    if (blocking) {
+        check(hipEventSynchronize(e1), "hipEventSynchronize");
+        float ms = 0.0f;
+        check(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
+        kerneltime_sum += ms;
+        if (measure) { tuner_.issued(pick.key, pick.gen, pick.cand); tuner_.record(pick.key, pick.gen, pick.cand, ms); }
+    } else if (measure) {
         slot.key = pick.key; slot.cand = pick.cand; slot.gen = pick.gen;
         tune_count_++;
         tuner_.issued(pick.key, pick.gen, pick.cand);                    // counted only now that its events are on the stream
     }
 }
-
-// TRILINEAR on 16-bit volumes: whole brick layers are the first guess -- and the per-axis copies are not built -- only while the
-// central ray keeps this share of its length along one volume axis: at 0.973 (a fifth of a voxel of shear per voxel) the
-// per-tile layer thickness already wins, 1.33 against 1.46 ms on cfg3; at 1.0 whole layers do, 1.17 against 1.20
-static constexpr double kTriWholeLayerAlignment = 0.985;
 
 // ---- the measured work model (launch_tuner.cpp): the results of the measurement launches whose events have completed
 void RendererCore::tuneCollect()
@@ -853,52 +852,22 @@ int RendererCore::importChoices(const void *buf, size_t bytes)
     return tuner_.importChoices(buf, bytes, (uint64_t)VR_BUILD_ID, device);
 }
 
-// the measured choice of this launch: the candidate kernels it could run (the part that needs the kernels' eligibility rules),
-// the tuner's pick among them (launch_tuner.cpp) applied to L
-void RendererCore::tuneChoose(const FrameParams &P, LaunchConfig &L)
+// the measured choice of this launch: the candidate kernels it could run (launch_plan.cpp), the tuner's pick among them
+// (launch_tuner.cpp) applied to L
+void RendererCore::tuneChoose(PreparedLaunch &F)
 {
-    tune_pick_ = {};
     tuneCollect();
-    const int prior = L.filter == 1 ? (L.tri_slab << 3) : ((L.sparse_shard ? 1 : 0) | (L.pipelined ? 2 : 0) | (L.short_batches ? 4 : 0));
+    const int prior = choiceBits(F.L);                                   // the heuristics' choice (what buildFrame / firstGuess left in L)
     last_choice_ = prior;
-    if (!autotune || force_generic != 0 || !L.tile_table) return;
-    // candidates, the heuristic's choice (what buildFrame / refreshTileSchedule left in L) first
-    int cand[LaunchTuner::kTuneCand], n = 0;
-    auto add = [&](int c) { for (int k = 0; k < n; k++) if (cand[k] == c) return; if (n < LaunchTuner::kTuneCand) cand[n++] = c; };
-    if (fast_path_eligible(P, L)) {
-        const bool relay_ok = !L.big_offsets && !(P.skip_empty != 0 && L.skip_grid != nullptr);
-        add(prior & (relay_ok ? 7 : 6));
-        add(P.alpha_scale >= 0.5f ? 4 : 2);                              // fast kernel: four-sample batches / pipelined loop
-        add(0);                                                          // fast kernel, plain loop
-        if (relay_ok) add(1);
-    } else if (L.filter == 1 && L.apron != nullptr && tri_slab_candidate(P, L)) {
-        // TRILINEAR: the LDS-staged kernel in its shapes, the batched kernel where it can run
-        add(prior);
-        add(1 << 3);
-        add(5 << 3);                                                     // three workgroups per CU: wins where the tiles' layers fit 53 KiB
-        // 16x16-pixel tiles on four wavefronts: launches whose 32x16-pixel tiles leave workgroup slots empty (two per CU).
-        // TRILINEAR: the small tile shape (16x16 pixels, four wavefronts, 40 KiB) is the FIRST GUESS where a tile's brick layers are small
-        // against its ring -- volumes up to 640 voxels along every axis (cfg1 shape 0.138 -> 0.118 ms, cfg2 shape 0.402 -> 0.381) -- and a
-        // CANDIDATE of the measured choice everywhere: on 1024^3 volumes it loses at the default pose (u16 1.12 -> 1.22 ms) and at strongly
-        // oblique ones (zenith 60 / azimuth 45: 1.55 -> 2.75), but wins over most of an orbit (u8: 0.92-1.02 against 1.01-1.11 ms at five of
-        // seven poses; u16 with the per-axis copies: 1.22 / 1.31 / 1.22 against 1.36 / 1.40 / 1.31; profiles/r06_trilinear_orbit.txt) -- which
-        // pose does which is exactly what the measurement is for.
-        if (L.tile_table_small != nullptr) add(6 << 3);
-        if (tri_path_candidate(P, L)) add(0);
-        if (L.apron_y != nullptr && L.apron_x != nullptr) {
-            add(3 << 3);
-            if (L.tile_table_tall != nullptr) add(4 << 3);
-        } else if (L.bytes_per_voxel == 1 && L.tile_table_tall != nullptr && viewAxisAlignment(P) < 0.92) {
-            add(4 << 3);                                                 // 8-bit volumes, oblique views: whole layers on 16x32-pixel tiles
-        }
-    }
+    if (!autotune || force_generic != 0 || !F.L.tile_table) return;
+    int cand[LaunchTuner::kTuneCand];
+    const int n = launchCandidates(F.P, F.L, prior, cand);
     if (n < 2) return;
-    const uint64_t key = launchTuneKey(P, L, launch_local_rows(P), tile_active_, prior);
-    tune_pick_ = tuner_.choose(key, cand, n, tune_count_, kTuneSlots);
-    if (!tune_pick_.decided) return;                                     // only passing through: L and last_choice_ stay the heuristics'
-    const int c = tune_pick_.cand;
-    L.sparse_shard = (c & 1) ? 1 : 0; L.pipelined = (c & 2) ? 1 : 0; L.short_batches = (c & 4) ? 1 : 0; L.tri_slab = (c >> 3) & 15;
-    last_choice_ = c | (tune_pick_.trial ? 256 : 0);                     // bit 8: a trial frame of a configuration still being explored
+    const uint64_t key = launchTuneKey(F.P, F.L, launch_local_rows(F.P), tiles_.active(), prior);
+    F.pick = tuner_.choose(key, cand, n, tune_count_, kTuneSlots);
+    if (!F.pick.decided) return;                                         // only passing through: L and last_choice_ stay the heuristics'
+    applyChoice(F.L, F.pick.cand);
+    last_choice_ = F.pick.cand | (F.pick.trial ? 256 : 0);               // bit 8: a trial frame of a configuration still being explored
 }
 
 // 12-bit packed copy (vr_set_pack12, default on): when the voxels of a bricked u16 volume span at most 4096
@@ -972,7 +941,7 @@ void RendererCore::residentBytes(uint64_t &volume, uint64_t &copies, uint64_t &o
     volume = d_vol_.bytes();
     copies = copies_.copiesBytes();
     other = d_fb_.bytes() + d_tf_.bytes() + d_spp_.bytes() + d_scratch_.bytes() + d_depth_.bytes() + d_values_.bytes() + copies_.skipGridBytes() +
-            d_loaded_.bytes() + meshBytes() + d_labels_.bytes() + d_rgba8_.bytes() + d_tile_table_.bytes() + d_tile_table_tall_.bytes() + d_tile_table_small_.bytes() + d_tile_work_.bytes();
+            d_loaded_.bytes() + meshBytes() + d_labels_.bytes() + d_rgba8_.bytes() + tiles_.bytes();
     for (const auto &q : d_present_) other += q.bytes();
 }
 
@@ -991,21 +960,9 @@ void RendererCore::refreshSkipGrid(FrameParams &P, LaunchConfig &L)
     // an interpolated value never exceeds its largest tap, and the classification of everything <= thresh is exactly zero
     const bool staged_tri = filter == 1 && tri_slab_candidate(P, L);
     if (!skip_empty || !(fast_path_eligible(P, L) || staged_tri)) return;
-    const int nx = res_dims_[0], ny = res_dims_[1], nz = res_dims_[2];
-    if (!staged_tri) {
-        // a batch of 8 samples must stay within +-1 cell of its middle sample: bound the voxel
-        // advance per step on every voxel axis (|dir| <= 1)
-        float max_delta = 0.0f;
-        const bool swz = (u_.view_bottom == 1 || u_.view_top == 1);
-        const float vdim[3] = {(float)nx, swz ? (float)nz : (float)ny, swz ? (float)ny : (float)nz};   // voxel axis behind each box axis
-        for (int a = 0; a < 3; a++) max_delta = std::max(max_delta, P.step * vdim[a] / P.ext[a]);
-        if (!(4.0f * max_delta + 0.6f <= 8.0f)) return;
-    }
+    if (!staged_tri && !nearestBatchWithinCells(P)) return;
     int thresh;
-    if (!zeroAlphaThreshold(P, staged_tri, thresh)) return;
-    const uint32_t cnx = (uint32_t)(nx + 7) / 8, cny = (uint32_t)(ny + 7) / 8, cnz = (uint32_t)(nz + 7) / 8;
-    const size_t cells = (size_t)cnx * cny * cnz;
-    if (cells * 2 >= (1ull << 32) || cnx >= (1u << 24) || (uint64_t)cny * cnz >= (1u << 24)) return;
+    if (!zeroAlphaThreshold(P, u_.min_val, u_.max_val, tf_lut_.empty() ? nullptr : tf_lut_.data(), staged_tri, thresh)) return;
     if (!ensureSkipGrid()) return;
     // nothing to skip at this threshold (a window that starts at the data's floor): the launch takes the instances without
     // skipping -- theirs are the leaner loops (staged TRILINEAR 3.8 %, its tiles on global taps 20 %, the NEAREST kernels a
@@ -1013,220 +970,58 @@ void RendererCore::refreshSkipGrid(FrameParams &P, LaunchConfig &L)
     if (thresh < (int)copies_.skipGridMin()) return;
     P.skip_empty = 1;
     P.skip_thresh = thresh;
-    P.cnx = (int32_t)cnx; P.cny = (int32_t)cny; P.cnz = (int32_t)cnz;
+    setSkipCells(P);
     L.skip_grid = copies_.skipGrid();
-    L.skip_grid_bytes = (uint32_t)(cells * sizeof(uint16_t));
-}
-
-// threshold: largest voxel value whose classification is exactly zero
-bool RendererCore::zeroAlphaThreshold(const FrameParams &P, bool whole_run, int &thresh) const
-{
-    if (P.alpha_scale == 0.0f) {
-        thresh = 65535;
-    } else if (tf_lut_.empty()) {
-        thresh = u_.min_val;                             // v = (clamp(t) - min)/den = 0  <=>  t <= min_val
-    } else {
-        int e = 0;
-        const int width = u_.max_val - u_.min_val;
-        // TRILINEAR classifies values BETWEEN the integers too: they reach every table entry up to the one of the largest tap
-        // (the index is monotone in the value), so there the whole leading run of entries has to be invisible
-        int zero_run = 0;
-        while (zero_run < 256 && tf_lut_[4 * zero_run + 3] * P.alpha_scale == 0.0f) zero_run++;
-        for (; e <= width; e++) {
-            const float s = (float)(u_.min_val + e);
-            const float v = (s - P.fmin) / P.fden;       // == the kernel's certified quotient
-            int idx = (int)std::floor(v * 255.0f + 0.5f);
-            idx = std::min(std::max(idx, 0), 255);
-            if (whole_run ? idx >= zero_run : tf_lut_[4 * idx + 3] * P.alpha_scale != 0.0f) break;
-        }
-        thresh = u_.min_val + e - 1;                     // e == 0: even the lowest entry is visible
-        if (e == 0) return false;
-    }
-    return true;
+    L.skip_grid_bytes = (uint32_t)((size_t)P.cnx * P.cny * P.cnz * sizeof(uint16_t));
 }
 
 bool RendererCore::ensureSkipGrid()
 {
-    const int nx = res_dims_[0], ny = res_dims_[1], nz = res_dims_[2];
-    const uint32_t cnx = (uint32_t)(nx + 7) / 8, cny = (uint32_t)(ny + 7) / 8, cnz = (uint32_t)(nz + 7) / 8;
-    const size_t cells = (size_t)cnx * cny * cnz;
-    if (cells * 2 >= (1ull << 32) || cnx >= (1u << 24) || (uint64_t)cny * cnz >= (1u << 24)) return false;
+    uint32_t c[3];
+    size_t cells;
+    if (!skipGridCells(res_dims_[0], res_dims_[1], res_dims_[2], c, cells)) return false;
     copies_.ensureSkipGrid(residentVolume(), cells);
     return true;
 }
 
-// Rebuild the longest-first block order when the camera / image / shard changed.  The
-// table is tiny (one word per 32x16-pixel tile) and is uploaded on the launch stream.
-void RendererCore::refreshTileSchedule(const FrameParams &P, LaunchConfig &L)
-{
-    L.tile_table = nullptr;
-    L.tile_table_blocks = 0;
-    L.tile_table_tall = nullptr;
-    L.tile_table_tall_blocks = 0;
-    L.tile_table_small = nullptr;
-    L.tile_table_small_blocks = 0;
-    if (!tile_order || !(fast_path_eligible(P, L) || tri_path_candidate(P, L) || tri_slab_candidate(P, L))) return;
-    const int rows = launch_local_rows(P);
-    if (rows <= 0) return;
-    // The table must list exactly the tiles of this image / shard (shape key); the camera only
-    // decides their ORDER, a speed heuristic.  While the camera moves (GUI orbit: every frame) the
-    // cached order is kept until the camera block has drifted noticeably, so that the host-side
-    // rebuild + upload (~0.7 ms at 1080p) is not paid per frame.
-    const uint64_t shape_key = tileScheduleKey(P, rows, false);
-    float drift = 0.0f;
-    for (int i = 0; i < 21; i++) drift = std::max(drift, std::fabs(P.cam[i] - tile_table_cam_[i]));
-    const bool need32 = filter == 1 && tri_slab_candidate(P, L) && (P.stripe_count <= 1 || P.stripe_rows % 32 == 0 || force_generic == 9);   // 16x32-pixel tiles for the staged trilinear kernel's tall shape
-    const bool need16 = filter == 1 && tri_slab_candidate(P, L);       // 16x16-pixel tiles for its small shape (four wavefronts; any stripe height that is a multiple of 16)
-    // empty-space skipping: the order follows the tiles' VISIBLE work (vr_kernels.hip: tile_visible_work_kernel); it changes with
-    // the threshold (window / transfer function), not only with the camera
-    // (NEAREST skips per ray and batch: every pose.  The staged TRILINEAR kernel skips per tile and brick layer, and its tiles
-    // that do not fit the ring skip nothing: where the view is oblique the estimate misjudges exactly the longest tiles -- the
-    // off-axis pose ran 1.46 / 1.55 / 2.2 ms depending on where they landed, and still 1.15 / 1.65 from one process to the next
-    // once those tiles skipped per batch -- so there the order stays the geometric one: 1.19-1.20 every time)
-    const bool skip_order = P.skip_empty != 0 && L.skip_grid != nullptr && (filter == 0 || viewAxisAlignment(P) >= 0.92);
-    // (in 32nds of the data's range: a window slider dragged under skipping would otherwise rebuild the table -- host sort, device
-    // estimate, two synchronisations -- on every frame; the order is a heuristic and changes gradually with the threshold)
-    const int64_t skip_sig = skip_order ? 1 + ((int64_t)std::max(P.skip_thresh, 0) * 32) / std::max<int64_t>((int64_t)exact_max_ + 1, 1) : 0;
-    if (shape_key != tile_table_key_ || !d_tile_table_ || !(drift <= 0.05f) || (need32 && tile_table_tall_blocks_ == 0) || (need16 && tile_table_small_blocks_ == 0) ||
-        skip_sig != tile_table_skip_sig_) {
-        std::vector<uint32_t> table;
-        std::vector<float> work, work_tall, work_small;
-        if (skip_order) {
-            // (one small kernel and a synchronous copy per table, only when the table is rebuilt; an empty sample costs about
-            // a seventh of a sampled one in both kernel families)
-            auto estimate = [&](unsigned tw, unsigned th, std::vector<float> &out) {
-                const size_t n = (size_t)((P.img_w + (int)tw - 1) / (int)tw) * (size_t)((rows + (int)th - 1) / (int)th);
-                d_tile_work_.ensure(2 * n, "tile work");
-                check(launch_tile_visible_work(P, L.skip_grid, rows, tw, th, 0.15f, filter == 1 ? 1 : 0, d_tile_work_.get(), stream()), "tile_visible_work_kernel");
-                std::vector<float> both(2 * n);
-                check(hipMemcpyAsync(both.data(), d_tile_work_.get(), 2 * n * sizeof(float), hipMemcpyDeviceToHost, stream()), "hipMemcpy(tile work)");
-                check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
-                out.resize(n);
-                for (size_t t = 0; t < n; t++) out[t] = both[2 * t + 1] > 0.0f ? std::min(both[2 * t] / both[2 * t + 1], 1.0f) : 1.0f;   // cost with skipping / without
-            };
-            estimate(kFastTileW, kFastTileH, work);
-            if (need32) estimate(16u, 32u, work_tall);
-            if (need16) estimate(16u, 16u, work_small);
-        }
-        tile_active_ = buildTileSchedule(P, rows, table, &tile_longest_, kFastTileH, kFastTileW, skip_order ? work.data() : nullptr);
-        // synchronous copies: the tables are pageable temporaries
-        check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
-        auto upload = [&](DeviceBuffer<uint32_t> &d, size_t &blocks, const std::vector<uint32_t> &t) {
-            d.ensure(t.size(), "tile table");
-            if (!t.empty()) check(hipMemcpy(d.get(), t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy(tile table)");
-            blocks = t.size();
-        };
-        upload(d_tile_table_, tile_table_blocks_, table);
-        tile_table_tall_blocks_ = 0;
-        if (need32) {
-            std::vector<uint32_t> tall;
-            (void)buildTileSchedule(P, rows, tall, nullptr, 32u, 16u, skip_order ? work_tall.data() : nullptr);
-            upload(d_tile_table_tall_, tile_table_tall_blocks_, tall);
-        }
-        tile_table_small_blocks_ = 0;
-        if (need16) {
-            std::vector<uint32_t> small;
-            tile_active_small_ = buildTileSchedule(P, rows, small, nullptr, 16u, 16u, skip_order ? work_small.data() : nullptr);
-            upload(d_tile_table_small_, tile_table_small_blocks_, small);
-        }
-        tile_table_key_ = shape_key;
-        tile_table_skip_sig_ = skip_sig;
-        std::memcpy(tile_table_cam_, P.cam, sizeof(tile_table_cam_));
-    }
-    L.tile_table = d_tile_table_.get();
-    L.tile_table_blocks = (uint32_t)tile_table_blocks_;
-    if (need32 && tile_table_tall_blocks_ > 0) { L.tile_table_tall = d_tile_table_tall_.get(); L.tile_table_tall_blocks = (uint32_t)tile_table_tall_blocks_; }
-    if (need16 && tile_table_small_blocks_ > 0) { L.tile_table_small = d_tile_table_small_.get(); L.tile_table_small_blocks = (uint32_t)tile_table_small_blocks_; }
-    // Kernel choice per launch (all bit-identical; measured on cfg3 after the checked-head fix, tools/pose_sweep.py and
-    // tools/shard_ms.py; `aligned` = central ray within ~23 degrees of a volume axis):
-    //   * relay kernel (4 wavefronts per 8x8 tile) for launches far from filling the chip -- fewer than 256 active
-    //     32x16 tiles when the view is aligned (N = 8 shard: 0.107 vs 0.142 ms), fewer than 1024 when it is oblique
-    //     (its rays are longer chains with more L1 misses per step: N = 2 shards 0.31-0.36 vs 0.36-0.47 ms);
-    //   * otherwise the fast kernel, with its software-pipelined batch loop unless the opacity scale says rays end
-    //     early (alpha >= 0.5: the speculative batch is wasted, 0.198 vs 0.189 ms): equal at the default pose
-    //     (0.454 ms), 3-14 % faster over oblique poses, 12 % at an N = 4 shard (0.163 vs 0.185 ms).
-    const bool aligned = viewAxisAlignment(P) >= 0.92;
-    // TRILINEAR, first guess (the work model then measures): the LDS-staged kernel (vr_tslab.hip) -- whole brick layers, two
-    // workgroups per CU -- when the view is aligned with a volume axis (cfg3 default pose: every tile staged, 1.25 vs 1.93 ms on
-    // the batched kernel) and for 8-bit volumes at every pose (80-byte slots: orbit poses 1.1-1.4 ms against 2.1).  A 16-bit
-    // volume's oblique layers do not fit three deep (240-400 bricks of 160 B): those views take the per-axis copies and half
-    // layers (round 4: orbit poses 1.43-1.62 ms against 2.9-3.4 whole-layer / 2.6-3.0 batched), on 16x32-pixel tiles with the
-    // ring's rows holding their own brick ranges when the view runs near a body diagonal of the volume (1.68 ms against 3.0).
-    if (force_generic == 0 && filter == 1 && tri_slab_candidate(P, L)) {
-        if (std::max(P.nx, std::max(P.ny, P.nz)) <= 640 && L.tile_table_small != nullptr) {
-            L.tri_slab = 6;                                              // small volumes: 16x16-pixel tiles (round 6)
-        } else if (viewAxisAlignment(P) >= kTriWholeLayerAlignment || L.bytes_per_voxel == 1) {
-            L.tri_slab = 1;
-        } else {
-            double r1, r2;
-            viewAxisRatios(P, r1, r2);
-            // 16x32-pixel tiles only where 32 consecutive LOCAL rows are 32 consecutive image rows: with cyclic stripes of 16
-            // rows a tall tile spans two stripes stripe_count*16 rows apart, its corner-ray hull (and its load plan) is that
-            // much taller, and nearly every tile would march unstaged (round-4 advisor)
-            const bool tall_ok = P.stripe_count <= 1 || P.stripe_rows % 32 == 0;
-            L.tri_slab = (r1 > 0.7 && r2 > 0.55 && tall_ok) ? 4 : 3;
-        }
-    }
-    // first guess of the work model (kernel variant 0 then measures, tuneChoose): the relay kernel pays when the launch is
-    // a single under-filled round of long serial rays -- few active tiles, scaled by how long the rays are (1045 samples
-    // on the configuration the 256 / 1024 were measured on; a 256^3 volume's 262-sample rays want 4x fewer tiles)
-    const double len_scale = std::min(1.0, std::max(0.15, tile_longest_ / 1000.0));
-    L.sparse_shard = ((double)tile_active_ < (aligned ? 256.0 : 1024.0) * len_scale) ? 1 : 0;
-    if (force_generic == 2) L.sparse_shard = 0;   // kernel variant 2: never the relay kernel
-    if (force_generic == 3) L.sparse_shard = 1;          // kernel variant 3: always (when the shape allows)
-    L.pipelined = (force_generic == 0 && P.alpha_scale < 0.5f) ? 1 : 0;
-    L.short_batches = (force_generic == 0 && P.alpha_scale >= 0.5f) ? 1 : 0;     // 0.174 vs 0.190 ms at alpha = 1 (cfg3)
-    if (force_generic == 5) { L.pipelined = 1; L.sparse_shard = 0; }   // kernel variant 5: fast kernel, pipelined loop, never the relay
-}
-
 void RendererCore::render()
 {
-    refuseIsoGreyAlpha();
-    requireDevice("render");
-    // the reference brackets glDispatchCompute with a GL_TIME_ELAPSED query and blocks
-    // on its result (src/RendererCore.cpp:149-153); same shape with HIP events
-    // (GL_TIME_ELAPSED covers the dispatch only: all host-side preparation happens first)
-    FrameParams P;
-    LaunchConfig L;
-    float4 *fb = prepareLaunch(P, L);
-    const LaunchTuner::Pick pick = tune_pick_;
-    tune_pick_ = {};
-    check(hipEventRecord(ev0_, stream()), "hipEventRecord");
-    check(launchKernel(P, L, fb, nullptr), "raymarch launch");
-    check(hipEventRecord(ev1_, stream()), "hipEventRecord");
-    check(hipEventSynchronize(ev1_), "hipEventSynchronize");
-    float ms = 0.0f;
-    check(hipEventElapsedTime(&ms, ev0_, ev1_), "hipEventElapsedTime");
-    kerneltime_sum += ms;
-    if (pick.measure) { tuner_.issued(pick.key, pick.gen, pick.cand); tuner_.record(pick.key, pick.gen, pick.cand, ms); }   // the blocking path measures anyway
+    launch(nullptr, true);
 }
 
-hipError_t RendererCore::launchKernel(const FrameParams &P, const LaunchConfig &L, float4 *fb, uint32_t *spp)
+hipError_t RendererCore::launchKernel(const PreparedLaunch &F, uint32_t *spp)
 {
-    if (reslice_enable_) {
+    const FrameParams &P = F.P;
+    const LaunchConfig &L = F.L;
+    switch (F.mode) {
+    case FrameMode::Reslice: {
         ResliceArgs A;
         std::memcpy(&A.g, reslice_geom_, sizeof(A.g));
         A.mode = reslice_mode_;
         A.n = reslice_n_;
         A.hu_offset = (datasize_bytes == 2 && (quirks & kQuirkU16Offset)) ? 1 : 0;
         A.values = d_values_.get();
-        return launch_reslice(P, L, A, d_vol_.get(), d_tf_.get(), fb, spp, stream(), &last_kernel_);
+        return launch_reslice(P, L, A, d_vol_.get(), d_tf_.get(), F.fb, spp, stream(), &last_kernel_);
     }
-    if (shadeFrame()) {
+    case FrameMode::Shaded: {
         ShadeArgs A;
         A.ambient = shade_k_[0]; A.diffuse = shade_k_[1]; A.specular = shade_k_[2];
         A.spec_squarings = 0;
         while ((1 << A.spec_squarings) < shade_shininess_) A.spec_squarings++;
-        A.skip_grid = shade_skip_grid_;
-        A.skip_thresh = shade_skip_thresh_;
-        return launch_raymarch_shade(P, L, A, d_vol_.get(), d_tf_.get(), fb, spp, stream(), &last_kernel_);
+        A.skip_grid = F.skip_grid;
+        A.skip_thresh = F.skip_thresh;
+        return launch_raymarch_shade(P, L, A, d_vol_.get(), d_tf_.get(), F.fb, spp, stream(), &last_kernel_);
     }
-    if (!iso_enable_) return launch_raymarch(P, L, d_vol_.get(), d_tf_.get(), fb, spp, stream(), &last_kernel_);
-    IsoArgs A;
-    A.iso_s = isoStored();
-    A.depth = d_depth_.get();
-    A.skip_grid = iso_skip_grid_;
-    return launch_raymarch_iso(P, L, A, d_vol_.get(), d_tf_.get(), fb, spp, stream(), &last_kernel_);
+    case FrameMode::Isosurface: {
+        IsoArgs A;
+        A.iso_s = isoStored();
+        A.depth = d_depth_.get();
+        A.skip_grid = F.skip_grid;
+        return launch_raymarch_iso(P, L, A, d_vol_.get(), d_tf_.get(), F.fb, spp, stream(), &last_kernel_);
+    }
+    case FrameMode::RayMarch: break;
+    }
+    return launch_raymarch(P, L, d_vol_.get(), d_tf_.get(), F.fb, spp, stream(), &last_kernel_);
 }
 
 // iso_s = float(iso + 1000) for 16-bit data under VR_QUIRK_U16_OFFSET (the window's own offset, setMinVal), float(iso) otherwise
@@ -1302,7 +1097,7 @@ void RendererCore::readResliceValues(float *values, size_t n_floats)
 
 void RendererCore::renderAsync()
 {
-    launch(nullptr);
+    launch(nullptr, false);
 }
 
 void RendererCore::synchronize()
@@ -1319,7 +1114,7 @@ void RendererCore::countSamples(uint64_t *total, uint32_t *per_pixel, size_t n_p
     if (per_pixel && n_pixels < n) throw std::invalid_argument("countSamples: per_pixel buffer too small");
     d_spp_.ensure(n, "spp");
     check(hipMemsetAsync(d_spp_.get(), 0, n * sizeof(uint32_t), stream()), "hipMemset(spp)");
-    launch(d_spp_.get());
+    launch(d_spp_.get(), false);
     std::vector<uint32_t> host(n);
     check(hipMemcpyAsync(host.data(), d_spp_.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()), "hipMemcpy(spp)");
     check(hipStreamSynchronize(stream()), "hipStreamSynchronize");

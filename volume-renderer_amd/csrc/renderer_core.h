@@ -16,6 +16,7 @@
 #include "camera.h"
 #include "device_buffer.h"
 #include "launch_tuner.h"
+#include "tile_tables.h"
 #include "volume_copies.h"
 #include "vr_frame.h"
 
@@ -27,6 +28,10 @@ struct NoDeviceError : std::runtime_error {
 struct IoError : std::runtime_error {
     using std::runtime_error::runtime_error;
 };
+
+// which of the four frame kernels a frame runs: the first-hit isosurface and the reslice mode exclude each other and come before
+// everything else; Shaded: gradient-lit compositing is on and the frame is not MIP; RayMarch: composite or MIP (vr_kernels.hip)
+enum class FrameMode { RayMarch, Isosurface, Reslice, Shaded };
 
 class RendererCore {
 public:
@@ -84,8 +89,8 @@ public:
     void *framebufferDevice() const { return ext_fb_ ? ext_fb_ : d_fb_.get(); }
     void setStream(hipStream_t s) { user_stream_ = s; }
     hipStream_t streamHandle() const { return stream(); }     // the stream the next launch goes to
-    bool greyMode() const { return tf_lut_.empty() && !iso_enable_; }   // r == g == b in every pixel (no transfer function, no isosurface; reslice and shaded composite frames without one are grey)
-    void prepareForLaunch() { FrameParams P; LaunchConfig L; (void)prepareLaunch(P, L); }   // certification, tile order, packed copy: host work a timed launch should not carry
+    bool greyMode() const { return tf_lut_.empty() && frameMode() != FrameMode::Isosurface; }   // r == g == b in every pixel (no transfer function, no isosurface; reslice and shaded composite frames without one are grey)
+    void prepareForLaunch() { (void)prepareLaunch(); }   // certification, tile order, packed copy: host work a timed launch should not carry
     void setExternalFramebuffer(void *p) { ext_fb_ = p; }
     void setRowRange(int b, int e) { row_begin_ = b; row_end_ = e; }
     void setRowStripes(int rows, int index, int count);
@@ -253,7 +258,12 @@ private:
     bool shade_enable_ = false;
     float shade_k_[3] = {0.15f, 0.65f, 0.2f};   // ambient, diffuse, specular (the isosurface mode's constants)
     int shade_shininess_ = 16;
-    bool shadeFrame() const { return shade_enable_ && !iso_enable_ && !reslice_enable_ && u_.is_MIP != 1; }   // the next frame is a shaded composite one
+    FrameMode frameMode() const   // of the next frame
+    {
+        if (iso_enable_) return FrameMode::Isosurface;
+        if (reslice_enable_) return FrameMode::Reslice;
+        return (shade_enable_ && u_.is_MIP != 1) ? FrameMode::Shaded : FrameMode::RayMarch;
+    }
     int stripe_rows_ = 0, stripe_index_ = 0, stripe_count_ = 1;
     bool fb_compact_ = false;
     int fb_format_ = 0;
@@ -274,26 +284,18 @@ private:
     void refreshSkipGrid(FrameParams &P, LaunchConfig &L);
     void refuseIsoGreyAlpha() const;
     bool ensureSkipGrid();                   // build the dilated cell-max grid if it is not resident; false = the volume is too large for it
-    const uint16_t *iso_skip_grid_ = nullptr;   // the grid the iso launch being prepared skips on (nullptr = no skipping)
-    // the largest stored value every sample at or below which classifies to alpha exactly 0 (composite mode, this frame's window,
-    // transfer function and alpha_scale); whole_run: the table's whole leading zero-alpha run must lie beyond it (TRILINEAR, whose
-    // values fall between the integers).  false: even the lowest value is visible
-    bool zeroAlphaThreshold(const FrameParams &P, bool whole_run, int &thresh) const;
-    const uint16_t *shade_skip_grid_ = nullptr;   // the grid the shaded launch being prepared skips on (nullptr = no skipping) ...
-    int shade_skip_thresh_ = 0;                   // ... and its threshold
-    hipError_t launchKernel(const FrameParams &P, const LaunchConfig &L, float4 *fb, uint32_t *spp);   // the ray-march, the iso, the reslice or the shaded kernel
-    DeviceBuffer<uint32_t> d_tile_table_;    // work-ordered block -> tile table (tile_schedule.h); grown only: *_blocks_ words of each are in use
-    DeviceBuffer<uint32_t> d_tile_table_tall_;   // the same for 16x32-pixel tiles (the staged trilinear kernel's tall shape); built with the table above
-    DeviceBuffer<uint32_t> d_tile_table_small_;  // the same for 16x16-pixel tiles (the staged trilinear kernel's four-wavefront shape)
-    size_t tile_table_blocks_ = 0, tile_table_tall_blocks_ = 0, tile_table_small_blocks_ = 0;
-    unsigned tile_active_small_ = 0;
-    uint64_t tile_table_key_ = 0;
-    int64_t tile_table_skip_sig_ = 0;        // what the order was built for: 0 = geometric ray lengths, threshold + 1 = visible work under empty-space skipping (-1: rebuild)
-    DeviceBuffer<float> d_tile_work_;        // per-tile cost estimates of that (scratch of refreshTileSchedule)
-    float tile_table_cam_[21] = {};          // camera block the cached order was built for
-    unsigned tile_active_ = 0;               // tiles with work in the cached schedule
-    double tile_longest_ = 0.0;              // expected samples of its longest ray
-    void refreshTileSchedule(const FrameParams &P, LaunchConfig &L);
+    // everything one launch needs, decided before it (prepareLaunch) and handed to it (launchKernel)
+    struct PreparedLaunch {
+        FrameParams P;                       // (both zeroed by buildFrame)
+        LaunchConfig L;
+        float4 *fb = nullptr;                // the colour target
+        FrameMode mode = FrameMode::RayMarch;
+        const uint16_t *skip_grid = nullptr; // the isosurface and the shaded kernel: the grid they skip on (nullptr = no skipping) ...
+        int skip_thresh = 0;                 // ... and the shaded kernel's threshold (the ray-march kernels carry theirs in P and L)
+        LaunchTuner::Pick pick;              // the tuner's decision (measure: the launch is a measurement)
+    };
+    hipError_t launchKernel(const PreparedLaunch &F, uint32_t *spp);   // the ray-march, the iso, the reslice or the shaded kernel
+    TileTables tiles_;                       // the work-ordered block -> tile tables the specialised kernels walk
     const char *last_kernel_ = "";
     bool tslab_warm_ = false;
     // ---- measured work model (kernel variant 0; launch_tuner.h): the tuner decides which candidate kernel a launch runs, this
@@ -303,11 +305,10 @@ private:
     struct TuneSlot { Event ev0, ev1; uint64_t key = 0, gen = 0; int cand = -1; };   // cand: the candidate VALUE (bit set), not its index in the entry's shuffled order
     TuneSlot tune_slot_[kTuneSlots];
     int tune_head_ = 0, tune_count_ = 0;     // ring of in-flight slots: oldest at tune_head_
-    LaunchTuner::Pick tune_pick_;            // the tuner's decision for the launch being prepared (measure: it is a measurement)
     int last_choice_ = 0;                    // candidate bits of the last launch (vr_get_launch_choice)
-    void tuneChoose(const FrameParams &P, LaunchConfig &L);
+    void tuneChoose(PreparedLaunch &F);
     void tuneCollect();
-    void noMeasuredChoice() { tune_pick_ = {}; last_choice_ = 0; }   // a frame of a mode with one kernel (isosurface, reslice, shaded)
+    void noMeasuredChoice() { last_choice_ = 0; }   // a frame of a mode with one kernel (isosurface, reslice, shaded)
 
     hipStream_t stream() const { return user_stream_ ? user_stream_ : own_stream_; }
     void requireDevice(const char *what) const;
@@ -322,10 +323,10 @@ private:
     void scanDatasetRange();
     bool certifyDivisor(float b);
     void buildFrame(FrameParams &P, LaunchConfig &L);
-    float4 *prepareLaunch(FrameParams &P, LaunchConfig &L);
+    PreparedLaunch prepareLaunch();
     void setSkipCells(FrameParams &P) const;
     void growFloatTarget(DeviceBuffer<float> &d, int fill, const char *name);
-    void launch(uint32_t *spp);
+    void launch(uint32_t *spp, bool blocking);   // blocking: timed into kerneltime_sum (render)
     void updateWorkgroups();
     void setMessage(const std::string &t, const std::string &m) { title = t; msg = m; }
 };

@@ -100,6 +100,19 @@ uint64_t tileScheduleKey(const FrameParams &P, int rows, bool with_camera)
     return hsh;
 }
 
+int64_t skipOrderSignature(int skip_thresh, int exact_max)
+{
+    return 1 + ((int64_t)std::max(skip_thresh, 0) * 32) / std::max<int64_t>((int64_t)exact_max + 1, 1);
+}
+
+bool tileTablesStale(const TileTablesBuilt &built, uint64_t shape_key, const float cam[21], int64_t skip_sig, bool need_tall, bool need_small)
+{
+    bool drifted = false;
+    for (int i = 0; i < 21; i++) drifted = drifted || !(std::fabs(cam[i] - built.cam[i]) <= 0.05f);   // (!(.. <= ..): a NaN in the camera block rebuilds)
+    return shape_key != built.shape_key || !built.table || drifted || (need_tall && !built.tall) || (need_small && !built.small) ||
+           skip_sig != built.skip_sig;
+}
+
 unsigned buildTileSchedule(const FrameParams &P, int rows, std::vector<uint32_t> &table, double *max_ray_samples, unsigned tile_h, unsigned tile_w,
                            const float *work_override)
 {

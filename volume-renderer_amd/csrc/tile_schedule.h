@@ -38,4 +38,21 @@ void viewAxisRatios(const FrameParams &P, double &mid_over_max, double &min_over
 // that decides WHICH tiles exist (image, shard, volume box) -- the camera only decides their order
 uint64_t tileScheduleKey(const FrameParams &P, int rows, bool with_camera = true);
 
+// ---- when cached tables (tile_tables.h) are built again
+// what an order under empty-space skipping was built for, in 32nds of the data's range: a window slider dragged under skipping
+// would otherwise rebuild the table -- host sort, device estimate, two synchronisations -- on every frame; the order is a
+// heuristic and changes gradually with the threshold.  Never 0, which stands for the geometric order
+int64_t skipOrderSignature(int skip_thresh, int exact_max);
+// what the cached tables were built for
+struct TileTablesBuilt {
+    bool table = false, tall = false, small = false;   // which tables hold blocks
+    uint64_t shape_key = 0;                  // tileScheduleKey(P, rows, false)
+    int64_t skip_sig = 0;                    // 0 = geometric ray lengths, skipOrderSignature() = visible work (-1: rebuild)
+    float cam[21] = {};                      // the camera block of the cached order
+};
+// The tables must list exactly the tiles of this image / shard (shape key); the camera only decides their ORDER, a speed
+// heuristic.  While the camera moves (GUI orbit: every frame) the cached order is kept until the camera block has drifted
+// noticeably, so that the host-side rebuild + upload (~0.7 ms at 1080p) is not paid per frame.
+bool tileTablesStale(const TileTablesBuilt &built, uint64_t shape_key, const float cam[21], int64_t skip_sig, bool need_tall, bool need_small);
+
 }  // namespace vr

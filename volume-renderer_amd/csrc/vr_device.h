@@ -238,7 +238,7 @@ static_assert(FAST_TF_WINDOW_MAX == FAST_LUT_MAX * 8 - FAST_TF_ENTRIES * 16, "vr
 // Address tables (ATAB): the byte offset of voxel (i,j,k) is X[i] + Y[j] + Z[k] in both layouts,
 // so the ~10 integer VALU ops of VoxelAddr become three LDS look-ups and one add; integer ops
 // issue at ~1.6x the cost of fp32 ops on gfx950 and are 40 % of the inner loop's issue time.
-constexpr int FAST_AXIS_TAB_MAX = 3072; // entries: nx + ny + nz (x 4 B = 12 KiB)
+// (FAST_AXIS_TAB_MAX, vr_frame.h: nx + ny + nz entries x 4 B = 12 KiB)
 // the same for volumes beyond 32-bit offsets (2048^3 = 6144 entries, 24 KiB); their classification table is
 // cut to 8 KiB -- 1024 (c,a) entries, or the 256 RGBA entries + 4096 index bytes -- so that three workgroups
 // still fit a CU

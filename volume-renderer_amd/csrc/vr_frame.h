@@ -31,6 +31,8 @@ constexpr uint64_t apron_voxels(int nx, int ny, int nz)
 // widest window (in voxel values) the specialised kernels classify through LDS with a transfer
 // function: one index byte per value behind the 256-entry RGBA table in a 32 KiB array
 constexpr int FAST_TF_WINDOW_MAX = 4096 * 8 - 256 * 16;
+// longest address tables the specialised kernels keep in LDS (vr_device.h: ATAB): nx + ny + nz entries
+constexpr int FAST_AXIS_TAB_MAX = 3072;
 
 struct FrameParams {
     float cam[21];                 // view_mat columns, eye, view_plane_dist

@@ -3,22 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch_plan.h"   // fast_path_eligible, tri_path_candidate, tri_slab_candidate, launch_local_rows
 #include "vr_frame.h"
 
 namespace vr {
 
-// true when (P, L) runs on the specialised NEAREST/composite/iterative kernel
-bool fast_path_eligible(const FrameParams &P, const LaunchConfig &L);
-// TRILINEAR in a grey mode with everything the batched trilinear kernel needs except the tile table
-bool tri_path_candidate(const FrameParams &P, const LaunchConfig &L);
-
-// TRILINEAR on the LDS-staged kernel (vr_tslab.hip): the trilinear path's preconditions with any mode (grey, MIP,
-// transfer function), the bricked layout with its apron copy resident, torus tables that fit LDS; volumes beyond
-// 32-bit offsets included
-bool tri_slab_candidate(const FrameParams &P, const LaunchConfig &L);
-
-// local image rows one launch covers (stripe padding included)
-int launch_local_rows(const FrameParams &P);
 // blocks of a launch whose 16x16-pixel tiles tile_of_block() deals out: every XCD gets ceil(tiles_y / 8) tile rows' worth of
 // slots; extras are padding
 static inline unsigned padded_blocks(unsigned tiles_x, unsigned tiles_y) { return ((tiles_y + 7u) / 8u) * tiles_x * 8u; }

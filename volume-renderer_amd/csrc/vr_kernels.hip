@@ -313,41 +313,8 @@ hipError_t launch_raymarch_tu3(VR_TU_ARGS) { return raymarch_tu<uint16_t, 1>(P, 
 #endif
 
 #if VR_TU_MAIN
-// The specialised kernel covers NEAREST + iterative accumulation with a non-degenerate
-// window whose divisions were certified and alpha_scale in [0,1]: grey-ramp composite,
-// grey-ramp MIP, and composite through a transfer-function table that fits LDS.
-// Everything else (TRILINEAR, closed-form accumulation, MIP + TF, ...) is generic.
-bool fast_path_eligible(const FrameParams &P, const LaunchConfig &L)
-{
-    const bool tf = P.tf_len > 1;
-    if (tf && !L.use_lut) return false;
-    return !L.generic && L.filter == 0 && P.accum == 0 && P.fden > 0.0f &&
-           P.max_val > P.min_val && L.divmode_win == DIV_CERT && L.divmode_tc != DIV_EXACT &&
-           P.alpha_scale >= 0.0f && P.alpha_scale <= 1.0f;
-}
-
-// TRILINEAR has a batched kernel for the grey modes: same preconditions as the fast path apart
-// from the filter, plus 32-bit offsets, address tables that fit LDS and a tile table
-bool tri_path_candidate(const FrameParams &P, const LaunchConfig &L)
-{
-    return !L.generic && L.filter == 1 && P.accum == 0 && P.tf_len <= 1 && P.fden > 0.0f && P.max_val > P.min_val &&
-           L.divmode_win == DIV_CERT && L.divmode_tc != DIV_EXACT && P.alpha_scale >= 0.0f && P.alpha_scale <= 1.0f &&
-           !L.big_offsets && P.nx + P.ny + P.nz <= FAST_AXIS_TAB_MAX;
-}
-
+// (which frames the specialised kernels take: launch_plan.cpp -- fast_path_eligible, tri_path_candidate, tri_slab_candidate)
 static bool tri_path_eligible(const FrameParams &P, const LaunchConfig &L) { return tri_path_candidate(P, L) && L.tile_table != nullptr; }
-
-// TRILINEAR on the LDS-staged kernel (vr_tslab.hip): every mode (the 256-entry transfer-function table sits in LDS), any
-// volume size (64-bit DMA addresses), the bricked layout; the apron copy must be resident (host: refreshApron)
-bool tri_slab_candidate(const FrameParams &P, const LaunchConfig &L)
-{
-    if (L.generic || L.filter != 1 || P.accum != 0 || !(P.fden > 0.0f) || !(P.max_val > P.min_val) || L.divmode_win != DIV_CERT ||
-        L.divmode_tc == DIV_EXACT || !(P.alpha_scale >= 0.0f && P.alpha_scale <= 1.0f) || L.layout != 1) return false;
-    if (P.tf_len > 256) return false;
-    const uint64_t bricks = (uint64_t)P.bnx * (uint64_t)P.bny * (uint64_t)P.bnz;
-    if (bricks >= (1ull << 32) || (uint64_t)P.bnx * (uint64_t)P.bny >= (1ull << 24)) return false;
-    return P.nx <= 32768 && P.ny <= 32768 && P.nz <= 32768;           // 16-bit brick indices in the load plan; plan and tables cover a tile's own range only
-}
 
 static bool tri_slab_selected(const FrameParams &P, const LaunchConfig &L)
 {
@@ -358,19 +325,6 @@ hipError_t launch_raymarch_slab_tri_u8(const FrameParams &P, const LaunchConfig 
                                        uint32_t *spp, hipStream_t st);
 hipError_t launch_raymarch_slab_tri_u16(const FrameParams &P, const LaunchConfig &L, const void *vol, const float4 *tf, float4 *fb,
                                         uint32_t *spp, hipStream_t st);
-
-int launch_local_rows(const FrameParams &P)
-{
-    int rows;
-    if (P.stripe_count > 1) {
-        const int nstripes_total = (P.img_h + P.stripe_rows - 1) / P.stripe_rows;
-        const int mine = (nstripes_total - P.stripe_index + P.stripe_count - 1) / P.stripe_count;
-        rows = mine * P.stripe_rows;
-    } else {
-        rows = P.row_end - P.row_begin;
-    }
-    return rows;
-}
 
 #if VR_TU == -1
 hipError_t launch_raymarch_tu0(VR_TU_ARGS);
