@@ -411,6 +411,49 @@ int vr_set_component_index_bits(vr_handle h, int bits);
 /* measurement aid: HIP-event time, in ms, of the kernels of the last successful vr_label_components (tile pass, seam pass,
    flatten, scan, labels, records; allocations, read-backs and host work excluded); 0 before the first */
 int vr_get_components_ms(vr_handle h, float *ms);
+/* Simplification of the resident mesh by vertex clustering, computed on the device (no reference equivalent; Rossignac and
+   Borrel's clustering, VTK's vtkQuadricClustering with an input vertex as the representative): vr_simplify_mesh replaces the
+   handle's mesh, whether vr_extract_isosurface or vr_extract_components made it, by its simplification.  vr_get_mesh_info
+   (the iso value is unchanged), vr_read_mesh, vr_save_mesh, vr_free_mesh and `other` of vr_get_resident_bytes then serve the
+   new mesh.  Every fp32 step is one correctly rounded operation in the order given, nothing contracted:
+   1. Input: the resident mesh, V vertices (positions in the spacing's units, all >= 0, and normals) and T triangles; `cell`,
+      the edge length of the cubic clustering cells in the same units.  The grid is anchored at the origin, voxel (0,0,0)'s centre.
+   2. Cell of a vertex: per axis q_a = p_a / cell (one division) and c_a = (int)floorf(q_a).  A q_a that is not below 2097152.0f
+      (2^21) -- or is negative or NaN, which no extraction produces -- is an error: VR_E_INVALID, a message for vr_take_message,
+      the mesh untouched.  Two vertices are in the same cluster when their three c_a are equal.
+   3. Representative: centre_a = ((float)c_a + 0.5f) * cell (the sum is exact, the product rounded once); d_a = p_a - centre_a;
+      dist = (d_z*d_z + d_y*d_y) + d_x*d_x.  A cluster's representative is its vertex of smallest dist, ties going to the lowest
+      vertex index (so coincident vertices, which the extraction produces where s_A == iso_s, resolve by index).  It is an input
+      vertex: it keeps its position and normal bits and stays on the isosurface.  Nothing is averaged.
+   4. Triangles: every index is replaced by its cluster's representative.  A triangle with two equal indices is dropped.  Of the
+      remaining triangles with the same unordered vertex set only the one of lowest input index is kept, with its own
+      orientation.  Kept triangles stay in input order.
+   5. Vertices: only representatives that a kept triangle references are kept, in ascending input index, renumbered
+      0 .. V'-1: the output vertices are rows of the input's position and normal arrays in their order, as with
+      vr_extract_components' sub-mesh.
+   6. Consequences: every output vertex is referenced; no two output vertices share a cell; every triangle has three different
+      indices and no two triangles have the same vertex set; simplifying the result again with the same cell gives the same
+      bytes; a cell larger than the mesh's extent gives the empty mesh with VR_OK; the empty mesh simplifies to the empty mesh.
+      Closedness and edge-manifoldness are NOT preserved (as with VTK's filter): a thin sheet may collapse onto itself, a
+      tunnel may close, an edge may end up with one or with more than two triangles.
+   7. State: the new arrays are built first and swapped in at the end; after any error the previous mesh is still there.  The
+      call changes no rendering state (window, modes, copies, launch choices, stream), keeps the labelling and queues no message
+      on success.  Work arrays live on the device and are freed before it returns: while the vertices are clustered 40 bytes a
+      vertex (keys and indices before and after the sort, distances, cluster numbers, representatives, run heads) plus 8 bytes a
+      cluster, then 12 bytes a vertex and 48 bytes a triangle (the triples before, between and after their two sorts, the two
+      orders, the kept flags) plus 4 bytes a cluster; in both stretches rocPRIM's sort scratch on top, which is at most one more
+      copy of the keys and values being sorted (12 bytes an element).  VR_E_NOMEM where that does not fit.
+   8. Errors, checked in this order: a host-only handle: VR_E_NO_DEVICE; cell not finite, not a normal number or <= 0:
+      VR_E_INVALID; no mesh: VR_E_INVALID; step 2's refusal; a device allocation that fails: VR_E_NOMEM.  n_vertices and
+      n_triangles may be NULL.
+   9. vr_get_mesh_simplification (any pointer may be NULL): after an extraction cell = 0 and the mesh's own counts; after a
+      simplification that call's cell and the counts of the mesh it was given; before the first mesh and after vr_free_mesh:
+      VR_E_INVALID.
+   10. vr_get_simplify_ms: measurement aid: HIP-event time, in ms, of the kernels and device sorts of the last successful
+      vr_simplify_mesh (allocations, read-backs and host work excluded); 0 before the first and after one of an empty mesh. */
+int vr_simplify_mesh(vr_handle h, float cell, uint64_t *n_vertices, uint64_t *n_triangles);
+int vr_get_mesh_simplification(vr_handle h, float *cell, uint64_t *source_vertices, uint64_t *source_triangles);
+int vr_get_simplify_ms(vr_handle h, float *ms);
 /* kernel selection: 0 = automatic (specialised kernels when the configuration allows; launches far from filling the
    chip -- fewer than 256 active 32x16 tiles, 1024 when the view is oblique to the volume axes -- use the 4-wavefront
    relay kernel; the fast kernel runs its software-pipelined batch loop unless alpha_scale >= 0.5),

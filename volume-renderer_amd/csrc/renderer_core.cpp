@@ -22,6 +22,7 @@
 #include "vr_smooth.h"
 #include "vr_components.h"
 #include "vr_mesh.h"
+#include "vr_simplify.h"
 #include "vr_kernels.h"
 
 namespace vr {
@@ -155,6 +156,7 @@ bool RendererCore::loadShader(std::string fn, bool reload)
         check(launch_warm_smooth(stream()), "module pre-load (smoothing)");
         check(launch_warm_mesh(stream()), "module pre-load (extraction)");
         check(launch_warm_components(stream()), "module pre-load (components)");
+        check(launch_warm_simplify(stream()), "module pre-load (simplification)");
         check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
         tslab_warm_ = false;
         if (filter == 1) warmTrilinear();

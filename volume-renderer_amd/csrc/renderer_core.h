@@ -160,6 +160,15 @@ public:
     // upper bound on the bytes of extractIsosurface's per-voxel arrays (vr_set_mesh_workspace; 9 bytes a voxel); 0: automatic --
     // 2 GiB or what the device has free; the extraction runs in z slabs that fit
     uint64_t mesh_workspace_limit = 0;
+    // simplification of the resident mesh by vertex clustering on cubic cells of edge `cell` (vr_simplify_mesh; vr_simplify.hip;
+    // DESIGN.md section 1.7): replaces the mesh, whichever extraction made it, by its simplification.  A cell that is not a
+    // normal number above 0, no mesh: std::invalid_argument; a coordinate / cell of 2^21 or more: a queued message and
+    // std::invalid_argument; an allocation that fails: DeviceMemoryError; in each case the previous mesh stays.  No rendering
+    // state changes and the labelling is kept.
+    void simplifyMesh(float cell, uint64_t *n_vertices, uint64_t *n_triangles);
+    // the cell of the simplification that made the resident mesh (0: an extraction did) and the counts of the mesh it was given
+    void meshSimplification(float *cell, uint64_t *source_vertices, uint64_t *source_triangles) const;
+    float lastSimplifyMs() const { return last_simplify_ms_; }   // HIP-event time of the last simplification's kernels and device sorts
     // connected components of the inside voxels (s >= iso) of the volume being rendered under the 14-neighbourhood of the
     // extraction's edge directions (vr_label_components; vr_components.hip).  The labels stay on the device
     // (4 bytes a voxel, under `other`), the records come to the host, where the selection is made.  Unlike the mesh the labelling
@@ -216,6 +225,9 @@ private:
     DeviceBuffer<float> d_mesh_pos_, d_mesh_nrm_;   // 3 floats a vertex
     DeviceBuffer<uint32_t> d_mesh_tri_;      // 3 indices a triangle
     float last_mesh_ms_ = 0.0f;
+    float mesh_cell_ = 0.0f;                 // meshSimplification
+    uint64_t mesh_src_nv_ = 0, mesh_src_nt_ = 0;
+    float last_simplify_ms_ = 0.0f;
     uint64_t meshBytes() const;              // device bytes of the mesh
     // the shared body of extractIsosurface and extractComponents; selected: launch_components_plane's bits or nullptr; ms: kernel time so far
     void extractMesh(int32_t iso, float iso_s, const uint64_t *selected, float ms, uint64_t *n_vertices, uint64_t *n_triangles);

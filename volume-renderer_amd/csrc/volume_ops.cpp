@@ -1,6 +1,7 @@
 // volume_ops.cpp -- RendererCore members that compute on the resident volume outside a frame: Gaussian smoothing
 // (vr_smooth_volume), isosurface extraction with its mesh (vr_extract_isosurface; section 1.5) and the
-// connected components with the filtered extraction (vr_label_components, vr_extract_components; section 1.6).
+// connected components with the filtered extraction (vr_label_components, vr_extract_components; section 1.6), and the mesh's
+// simplification by vertex clustering (vr_simplify_mesh; section 1.7).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -9,6 +10,7 @@
 #include "renderer_core.h"
 #include "vr_components.h"
 #include "vr_mesh.h"
+#include "vr_simplify.h"
 #include "vr_smooth.h"
 
 namespace vr {
@@ -232,9 +234,143 @@ void RendererCore::extractMesh(int32_t iso, float iso_s, const uint64_t *selecte
     freeMesh();
     d_mesh_pos_ = std::move(pos); d_mesh_nrm_ = std::move(nrm); d_mesh_tri_ = std::move(tri);
     mesh_nv_ = nv; mesh_nt_ = nt; mesh_iso_ = iso; mesh_valid_ = true;
+    mesh_cell_ = 0.0f; mesh_src_nv_ = nv; mesh_src_nt_ = nt;               // (meshSimplification: not simplified)
     last_mesh_ms_ = ms;
     if (n_vertices) *n_vertices = nv;
     if (n_triangles) *n_triangles = nt;
+}
+
+// ---------------------------------------------------------------- simplification (vr_simplify_mesh)
+// Three stretches of kernels with a read-back after each, because the sizes of what follows depend on it: the extent (the key
+// bits; step 2's refusal), the clusters (their number K sizes the winners and the triangles' keys), the kept counts (the new
+// mesh).  The arrays of a stretch are freed as soon as nothing reads them; the new mesh is swapped in at the very end.
+void RendererCore::simplifyMesh(float cell, uint64_t *n_vertices, uint64_t *n_triangles)
+{
+    requireDevice("simplifyMesh");
+    if (!std::isnormal(cell) || !(cell > 0.0f)) throw std::invalid_argument("simplifyMesh: cell must be a finite, normal number above 0");
+    if (!mesh_valid_) throw std::invalid_argument("simplifyMesh: no isosurface has been extracted");
+    const uint64_t nv = mesh_nv_, nt = mesh_nt_;
+    uint64_t new_nv = 0, new_nt = 0;
+    float ms = 0.0f;
+    DeviceBuffer<float> pos, nrm;                        // the new mesh
+    DeviceBuffer<uint32_t> tri;
+    auto bitsOf = [](uint64_t m) { uint32_t b = 0; while (m) { b++; m >>= 1; } return b; };
+    if (nv > 0 && nt > 0) {
+        const float *const d_pos = d_mesh_pos_.get(), *const d_nrm = d_mesh_nrm_.get();
+        const uint32_t *const d_tri = d_mesh_tri_.get();
+        DeviceBuffer<uint8_t> temp;
+        auto scratch = [&](size_t bytes) { if (temp.bytes() < bytes || !temp) temp.allocOrNoMemory(bytes ? bytes : 16, "simplifyMesh: hipMalloc(sort scratch)"); };
+        // ---- the extent
+        DeviceBuffer<uint32_t> stats;
+        stats.allocOrNoMemory(4, "simplifyMesh: hipMalloc(extent)");
+        hipError_t e = hipMemsetAsync(stats.get(), 0, 16, stream());
+        if (e == hipSuccess) e = hipEventRecord(ev0_, stream());
+        if (e == hipSuccess) e = launch_simplify_extent(d_pos, nv, cell, stats.get(), stream());
+        check(finishTimed(e, ms), "simplification kernels (extent)");
+        uint32_t ext[4];
+        check(hipMemcpy(ext, stats.get(), sizeof(ext), hipMemcpyDeviceToHost), "hipMemcpy(D2H extent)");
+        if (ext[3]) {
+            setMessage("Error!", "The mesh spans 2^21 clustering cells or more along an axis at this cell size. Choose a larger cell.");
+            throw std::invalid_argument("simplifyMesh: a vertex coordinate divided by cell is not in [0, 2^21)");
+        }
+        const uint32_t bx = bitsOf(ext[0]), by = bitsOf(ext[1]), bz = bitsOf(ext[2]);
+        // ---- the clusters
+        DeviceBuffer<uint32_t> cluster, rep;             // per vertex; kept until the mesh is written
+        cluster.allocOrNoMemory(nv, "simplifyMesh: hipMalloc(clusters)");
+        rep.allocOrNoMemory(nv, "simplifyMesh: hipMalloc(representatives)");
+        uint32_t K = 0;
+        {
+            const uint32_t key_bits = std::max(bx + by + bz, 1u);
+            DeviceBuffer<uint64_t> key, key_sorted;
+            DeviceBuffer<uint32_t> index, index_sorted, dist, head;
+            DeviceBuffer<unsigned long long> winner;
+            key.allocOrNoMemory(nv, "simplifyMesh: hipMalloc(keys)");
+            key_sorted.allocOrNoMemory(nv, "simplifyMesh: hipMalloc(sorted keys)");
+            index.allocOrNoMemory(nv, "simplifyMesh: hipMalloc(indices)");
+            index_sorted.allocOrNoMemory(nv, "simplifyMesh: hipMalloc(sorted indices)");
+            dist.allocOrNoMemory(nv, "simplifyMesh: hipMalloc(distances)");
+            head.allocOrNoMemory(nv, "simplifyMesh: hipMalloc(run heads)");
+            const size_t sort_bytes = simplify_sort64_temp_bytes(nv, key_bits), scan_bytes = simplify_scan_temp_bytes(nv);
+            scratch(std::max(sort_bytes, scan_bytes));
+            e = hipEventRecord(ev0_, stream());
+            if (e == hipSuccess) e = launch_simplify_keys(d_pos, nv, cell, bx, by, key.get(), index.get(), dist.get(), stream());
+            if (e == hipSuccess) e = launch_simplify_sort64(temp.get(), temp.bytes(), key.get(), key_sorted.get(), index.get(), index_sorted.get(), nv, key_bits, stream());
+            if (e == hipSuccess) e = launch_simplify_heads(key_sorted.get(), nv, head.get(), stream());
+            if (e == hipSuccess) e = launch_simplify_scan(head.get(), nv, true, temp.get(), temp.bytes(), stream());
+            check(finishTimed(e, ms), "simplification kernels (clusters)");
+            check(hipMemcpy(&K, head.get() + (nv - 1), sizeof(K), hipMemcpyDeviceToHost), "hipMemcpy(D2H clusters)");
+            key.reset(); key_sorted.reset(); index.reset();
+            winner.allocOrNoMemory(K, "simplifyMesh: hipMalloc(winners)");
+            e = hipMemsetAsync(winner.get(), 0xff, winner.bytes(), stream());
+            if (e == hipSuccess) e = hipEventRecord(ev0_, stream());
+            if (e == hipSuccess) e = launch_simplify_winners(index_sorted.get(), head.get(), dist.get(), nv, cluster.get(), winner.get(), stream());
+            if (e == hipSuccess) e = launch_simplify_representatives(cluster.get(), winner.get(), nv, rep.get(), stream());
+            check(finishTimed(e, ms), "simplification kernels (representatives)");
+        }
+        // ---- the triangles
+        const uint32_t kb = bitsOf(K - 1);
+        DeviceBuffer<uint32_t> keep, kept;               // nt + 1 and nv + 1 words: flags, then their exclusive sums
+        keep.allocOrNoMemory(nt + 1, "simplifyMesh: hipMalloc(kept triangles)");
+        kept.allocOrNoMemory(nv + 1, "simplifyMesh: hipMalloc(kept vertices)");
+        {
+            DeviceBuffer<uint64_t> ab, ab_ordered, ab_sorted;
+            DeviceBuffer<uint32_t> c, c_sorted, index, order1, order2, used;
+            ab.allocOrNoMemory(nt, "simplifyMesh: hipMalloc(triples)");
+            ab_ordered.allocOrNoMemory(nt, "simplifyMesh: hipMalloc(ordered triples)");
+            ab_sorted.allocOrNoMemory(nt, "simplifyMesh: hipMalloc(sorted triples)");
+            c.allocOrNoMemory(nt, "simplifyMesh: hipMalloc(third corners)");
+            c_sorted.allocOrNoMemory(nt, "simplifyMesh: hipMalloc(sorted third corners)");
+            index.allocOrNoMemory(nt, "simplifyMesh: hipMalloc(triangle indices)");
+            order1.allocOrNoMemory(nt, "simplifyMesh: hipMalloc(first order)");
+            order2.allocOrNoMemory(nt, "simplifyMesh: hipMalloc(second order)");
+            used.allocOrNoMemory(K, "simplifyMesh: hipMalloc(used clusters)");
+            const uint32_t c_bits = std::max(kb, 1u), ab_bits = std::max(2 * kb, 1u);
+            scratch(std::max(std::max(simplify_sort32_temp_bytes(nt, c_bits), simplify_sort64_temp_bytes(nt, ab_bits)),
+                             std::max(simplify_scan_temp_bytes(nt + 1), simplify_scan_temp_bytes(nv + 1))));
+            e = hipMemsetAsync(keep.get(), 0, keep.bytes(), stream());
+            if (e == hipSuccess) e = hipMemsetAsync(used.get(), 0, used.bytes(), stream());
+            if (e == hipSuccess) e = hipEventRecord(ev0_, stream());
+            if (e == hipSuccess) e = launch_simplify_triples(d_tri, nt, cluster.get(), kb, ab.get(), c.get(), index.get(), stream());
+            if (e == hipSuccess) e = launch_simplify_sort32(temp.get(), temp.bytes(), c.get(), c_sorted.get(), index.get(), order1.get(), nt, c_bits, stream());
+            if (e == hipSuccess) e = launch_simplify_gather(ab.get(), order1.get(), nt, ab_ordered.get(), stream());
+            if (e == hipSuccess) e = launch_simplify_sort64(temp.get(), temp.bytes(), ab_ordered.get(), ab_sorted.get(), order1.get(), order2.get(), nt, ab_bits, stream());
+            if (e == hipSuccess) e = launch_simplify_keep(ab_sorted.get(), order2.get(), c.get(), nt, kb, keep.get(), used.get(), stream());
+            if (e == hipSuccess) e = launch_simplify_kept_vertices(rep.get(), cluster.get(), used.get(), nv, kept.get(), stream());
+            if (e == hipSuccess) e = launch_simplify_scan(keep.get(), nt + 1, false, temp.get(), temp.bytes(), stream());
+            if (e == hipSuccess) e = launch_simplify_scan(kept.get(), nv + 1, false, temp.get(), temp.bytes(), stream());
+            check(finishTimed(e, ms), "simplification kernels (triangles)");
+        }
+        uint32_t totals[2];
+        check(hipMemcpy(&totals[0], kept.get() + nv, 4, hipMemcpyDeviceToHost), "hipMemcpy(D2H kept vertices)");
+        check(hipMemcpy(&totals[1], keep.get() + nt, 4, hipMemcpyDeviceToHost), "hipMemcpy(D2H kept triangles)");
+        new_nv = totals[0]; new_nt = totals[1];
+        // ---- the new mesh
+        if (new_nt > 0) {
+            pos.allocOrNoMemory(new_nv * 3, "simplifyMesh: hipMalloc(positions)");
+            nrm.allocOrNoMemory(new_nv * 3, "simplifyMesh: hipMalloc(normals)");
+            tri.allocOrNoMemory(new_nt * 3, "simplifyMesh: hipMalloc(triangles)");
+            e = hipEventRecord(ev0_, stream());
+            if (e == hipSuccess) e = launch_simplify_emit_vertices(d_pos, d_nrm, kept.get(), nv, pos.get(), nrm.get(), stream());
+            if (e == hipSuccess) e = launch_simplify_emit_triangles(d_tri, keep.get(), nt, rep.get(), kept.get(), tri.get(), stream());
+            check(finishTimed(e, ms), "simplification kernels (emit)");
+        }
+    }
+    const int32_t iso = mesh_iso_;
+    freeMesh();
+    d_mesh_pos_ = std::move(pos); d_mesh_nrm_ = std::move(nrm); d_mesh_tri_ = std::move(tri);
+    mesh_nv_ = new_nv; mesh_nt_ = new_nt; mesh_iso_ = iso; mesh_valid_ = true;
+    mesh_cell_ = cell; mesh_src_nv_ = nv; mesh_src_nt_ = nt;
+    last_simplify_ms_ = ms;
+    if (n_vertices) *n_vertices = new_nv;
+    if (n_triangles) *n_triangles = new_nt;
+}
+
+void RendererCore::meshSimplification(float *cell, uint64_t *source_vertices, uint64_t *source_triangles) const
+{
+    if (!mesh_valid_) throw std::invalid_argument("meshSimplification: no isosurface has been extracted");
+    if (cell) *cell = mesh_cell_;
+    if (source_vertices) *source_vertices = mesh_src_nv_;
+    if (source_triangles) *source_triangles = mesh_src_nt_;
 }
 
 void RendererCore::meshInfo(int32_t *iso, uint64_t *n_vertices, uint64_t *n_triangles) const

@@ -429,6 +429,23 @@ int vr_get_mesh_ms(vr_handle h, float *ms)
     return VR_OK;
 }
 
+int vr_simplify_mesh(vr_handle h, float cell, uint64_t *n_vertices, uint64_t *n_triangles)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.simplifyMesh(cell, n_vertices, n_triangles); });
+}
+
+int vr_get_mesh_simplification(vr_handle h, float *cell, uint64_t *source_vertices, uint64_t *source_triangles)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.meshSimplification(cell, source_vertices, source_triangles); });
+}
+
+int vr_get_simplify_ms(vr_handle h, float *ms)
+{
+    if (!h || !ms) return VR_E_INVALID;
+    *ms = h->core.lastSimplifyMs();
+    return VR_OK;
+}
+
 int vr_label_components(vr_handle h, int32_t iso_value, uint64_t *n_components)
 {
     return guarded(h, [&](vr::RendererCore &c) { c.labelComponents(iso_value, n_components); });

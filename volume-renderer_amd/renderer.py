@@ -137,6 +137,9 @@ def load_library() -> C.CDLL:
         "vr_free_mesh": (i32, [h]),
         "vr_set_mesh_workspace": (i32, [h, C.c_uint64]),
         "vr_get_mesh_ms": (i32, [h, C.POINTER(f32)]),
+        "vr_simplify_mesh": (i32, [h, f32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "vr_get_mesh_simplification": (i32, [h, C.POINTER(f32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "vr_get_simplify_ms": (i32, [h, C.POINTER(f32)]),
         "vr_label_components": (i32, [h, i32, C.POINTER(C.c_uint64)]),
         "vr_get_components_info": (i32, [h, C.POINTER(i32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "vr_read_components": (i32, [h, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_uint64]),
@@ -711,6 +714,25 @@ class RendererCore:
         """HIP-event time of the last extractIsosurface's kernels, ms"""
         ms = C.c_float(0.0)
         self._check(self._lib.vr_get_mesh_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def simplifyMesh(self, cell):
+        """vr_simplify_mesh: replaces the resident mesh by its vertex-clustering simplification on cubic cells of edge `cell`
+        (the spacing's units): one input vertex per cell, collapsed and repeated triangles dropped.  Returns (vertices, triangles)."""
+        nv, nt = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.vr_simplify_mesh(self._h, C.c_float(float(cell)), C.byref(nv), C.byref(nt)))
+        return int(nv.value), int(nt.value)
+
+    def meshSimplification(self):
+        """how the resident mesh was made: dict(cell, source_vertices, source_triangles); cell 0: by an extraction"""
+        cell, nv, nt = C.c_float(0.0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.vr_get_mesh_simplification(self._h, C.byref(cell), C.byref(nv), C.byref(nt)))
+        return dict(cell=float(cell.value), source_vertices=int(nv.value), source_triangles=int(nt.value))
+
+    def simplifyMs(self) -> float:
+        """HIP-event time of the last simplifyMesh's kernels and device sorts, ms"""
+        ms = C.c_float(0.0)
+        self._check(self._lib.vr_get_simplify_ms(self._h, C.byref(ms)))
         return float(ms.value)
 
     def labelComponents(self, iso) -> int:
