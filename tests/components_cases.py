@@ -95,6 +95,79 @@ def seam_pairs(n=72, boundaries=(4, 8, 16, 32, 64), dtype=np.uint8):
     return vol, components
 
 
+CHUNK = 8192                                                # voxels, in linear order, that one workgroup of the records pass folds
+REC_SLOTS = 1024                                            # labels its table holds; a run of a further label goes straight to memory
+TILE = (32, 8, 4)                                           # the tile pass's tile (x, y, z)
+
+
+def lattice(shape_xyz, dtype=np.uint8):
+    """(x + y + z) % 4 == 0.  Each of the seven directions changes x + y + z by 1, 2 or 3, so no two lattice voxels are adjacent:
+    every one is its own component, a quarter of all voxels -- 2048 labels in each full 8192-voxel chunk."""
+    nx, ny, nz = shape_xyz
+    z, y, x = np.mgrid[0:nz, 0:ny, 0:nx]
+    return np.where((x + y + z) % 4 == 0, ON, 0).astype(dtype)
+
+
+def first_n_per_chunk(mask: np.ndarray, n, chunk=CHUNK):
+    """`mask` (a volume; set = non-zero) with only the first n set voxels, in linear order, of every `chunk` consecutive voxels"""
+    flat = mask.reshape(-1)
+    on = np.zeros(-(-flat.size // chunk) * chunk, dtype=np.int64)
+    on[:flat.size] = flat != 0
+    rank = np.cumsum(on.reshape(-1, chunk), axis=1).reshape(-1)[:flat.size]      # 1-based among its chunk's set voxels
+    return np.where((flat != 0) & (rank <= n), flat, 0).astype(mask.dtype).reshape(mask.shape)
+
+
+def y_lines(shape_xyz=(4096, 2, 4), dtype=np.uint8):
+    """x even and z even, every y: with ny = 2 each (x, z) column is a two-voxel component whose voxels are nx apart in linear
+    order -- two separate runs, and with nx * ny = 8192 both in the same chunk"""
+    nx, ny, nz = shape_xyz
+    vol = np.zeros((nz, ny, nx), dtype=dtype)
+    vol[0::2, :, 0::2] = ON
+    return vol
+
+
+def solid_with_hole(shape_xyz=(70, 66, 68), second_block=False, dtype=np.uint8):
+    """everything inside except the box x in [10, 60), y in [20, 40), z in [30, 34): one component whose box is the volume and
+    whose surface is the hole's.  second_block: a second cavity x in [3, 67), y in [5, 61), z in [40, 64) that holds, one voxel
+    clear of its walls all round, a solid block of its own -- two components, whole tiles in each, the surface still closed."""
+    nx, ny, nz = shape_xyz
+    vol = np.full((nz, ny, nx), ON, dtype=dtype)
+    vol[30:34, 20:40, 10:60] = 0
+    if second_block:
+        assert nx >= 70 and ny >= 66 and nz >= 68
+        vol[40:64, 5:61, 3:67] = 0
+        vol[42:62, 7:59, 5:65] = ON
+    return vol
+
+
+def lattice_under_a_slab(stem_from, shape_xyz=(64, 16, 24), dtype=np.uint8):
+    """one-voxel components and one large one in the same chunk: the lattice in the rows y < 12 of the planes z < 8 (192 a plane,
+    1536 in the first chunk), every plane z >= 10 solid, and a stem -- the rows y >= 13 of the planes stem_from <= z < 10 -- that
+    brings the slab's component down into the first chunk.  Row 12 keeps the stem clear of the lattice.  With stem_from = 0 the
+    large component's first run comes before the first chunk's 1024th label, with stem_from = 6 after its 1344th."""
+    nx, ny, nz = shape_xyz
+    vol = np.zeros((nz, ny, nx), dtype=dtype)
+    vol[:8, :12] = lattice((nx, 12, 8), dtype)
+    vol[10:] = ON
+    vol[stem_from:10, 13:] = ON
+    return vol
+
+
+def labels_per_chunk(labels: np.ndarray, chunk=CHUNK) -> np.ndarray:
+    """the number of distinct non-zero labels in every `chunk` consecutive entries of the flat label array"""
+    flat = labels.reshape(-1)
+    return np.array([np.count_nonzero(np.unique(flat[at:at + chunk])) for at in range(0, flat.size, chunk)], dtype=np.int64)
+
+
+def full_tiles(inside: np.ndarray, tile=TILE) -> int:
+    """the number of tile-aligned tiles (x, y, z) that lie wholly in the volume [z, y, x] and are all inside"""
+    tx, ty, tz = tile
+    nz, ny, nx = inside.shape
+    mz, my, mx = nz // tz, ny // ty, nx // tx
+    whole = np.asarray(inside, dtype=bool)[:mz * tz, :my * ty, :mx * tx].reshape(mz, tz, my, ty, mx, tx)
+    return int(whole.all(axis=(1, 3, 5)).sum())
+
+
 def vertex_labels(inside: np.ndarray, labels: np.ndarray) -> np.ndarray:
     """The extraction's vertex list restated in numpy: for each direction d the voxel pairs (A, A + e_d) with differing inside
     bits, in the order (owner A's linear index, d).  Returns each vertex's label: that of its inside endpoint."""

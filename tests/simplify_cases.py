@@ -19,6 +19,12 @@ def cells_of(pos: np.ndarray, cell) -> np.ndarray:
     return np.floor(q).astype(np.int64)
 
 
+def key_bits(pos: np.ndarray, cell) -> list:
+    """[bx, by, bz]: the bits the largest cell index on each axis needs -- the widths of the three fields an implementation may
+    pack into one sort key (0: every vertex is in cell 0 on that axis)"""
+    return [int(m).bit_length() for m in cells_of(pos, cell).max(axis=0)]
+
+
 def numpy_simplify(mesh, cell):
     """the definition with lexsort and unique: returns ((positions, normals, triangles), rows)"""
     pos, nrm, tri = mesh
@@ -91,3 +97,38 @@ def ball_volume(n=64, radius=24.0):
     z, y, x = np.meshgrid(*(np.arange(n, dtype=np.float64),) * 3, indexing="ij")
     d = np.sqrt((x - (n - 1) / 2) ** 2 + (y - (n - 1) / 2) ** 2 + (z - (n - 1) / 2) ** 2)
     return np.clip(np.rint(128.0 + 8.0 * (radius - d)), 0, 255).astype(np.uint8)
+
+
+# ---------------------------------------------------------------- cells that make the packed key wide, or an axis of it empty
+# the largest cell on extents of 39 whose largest quotient is still below 2^21: the accepting neighbour of the refusal
+LARGEST_KEY_CELL = float(np.float32(39.0) / np.float32(2097151.0))
+# name -> (volume, iso, spacing).  The ties volume's thousands of coincident vertices share a cell however small it is.
+KEY_VOLUMES = {
+    "ties": (lambda: ties_volume((40, 38, 36), 100, 5), 100, (1.0, 1.0, 1.0)),
+    "ties, unequal": (lambda: ties_volume((40, 38, 36), 100, 5), 100, SPACING),
+    "flat z": (lambda: random_volume((70, 66, 2), np.uint8, 3), 128, (1.0, 1.0, 0.25)),
+    "flat x": (lambda: random_volume((2, 66, 70), np.uint8, 3), 128, (0.25, 1.0, 1.0)),
+}
+# (volume, cell, [bx, by, bz])
+KEY_CASES = [
+    ("ties", 0.01, [12, 12, 12]),                           # 36 bits: the shifts cross bit 31
+    # 39 bits on a power of two: vertices half a voxel apart along z differ only in bit 32 of the key and above, so a key that
+    # lost those bits would merge them (at 0.01 the ties volume has no two vertices that only such bits tell apart)
+    ("ties", 2.0 ** -7, [13, 13, 13]),
+    ("ties", 1e-4, [19, 19, 19]),                           # 57 bits
+    ("ties", LARGEST_KEY_CELL, [21, 21, 21]),               # 63 bits: the widest key there is
+    ("ties, unequal", 1e-4, [18, 19, 20]),
+    ("flat z", 0.3, [8, 8, 0]),                             # no bits for z
+    ("flat z", 1.5, [6, 6, 0]),
+    ("flat x", 0.3, [0, 8, 8]),                             # no bits for x: y is shifted by 0
+    ("flat x", 1.5, [0, 6, 6]),
+]
+KEY_CASE_IDS = [f"{name}, {sum(bits)} bits" for name, cell, bits in KEY_CASES]
+
+
+def assert_key_case(pos: np.ndarray, name, cell, bits):
+    """the case exists: the vertices `pos` of KEY_VOLUMES[name]'s mesh need exactly `bits` at `cell`"""
+    assert key_bits(pos, cell) == bits, (name, cell, key_bits(pos, cell))
+    if cell == LARGEST_KEY_CELL:
+        assert int(cells_of(pos, cell).max()) < 2 ** 21 and float(pos.max()) == 39.0
+        assert np.float32(39.0) / np.float32(cell) > np.float32(2 ** 21 - 2)       # ... and no cell could be smaller by much

@@ -160,6 +160,123 @@ def test_the_seam_volume_has_its_closed_form_count(complib):
     assert rec["voxels"].size == components and int(rec["voxels"].sum()) == int((vol == K.ON).sum())
 
 
+# ---------------------------------------------------------------- volumes for the branches no random volume reaches
+# (tests/test_components_gpu.py runs the kernels on them; here the restatement has its known answers and the cases exist)
+def linear_of(vol):
+    return np.flatnonzero(vol.reshape(-1))
+
+
+def xyz_of(lin, vol):
+    nz, ny, nx = vol.shape
+    return np.stack([lin % nx, lin // nx % ny, lin // (nx * ny)], axis=1)
+
+
+def test_the_lattice_is_one_component_per_voxel(complib):
+    vol = K.lattice((64, 16, 16))
+    labels, rec = comp_ref.label(complib, vol, K.ISO)
+    lin = linear_of(vol)
+    assert lin.size == 4096 == rec["voxels"].size and np.all(rec["voxels"] == 1)
+    assert np.array_equal(rec["first_voxel"], lin.astype(np.uint64))           # ascending linear order
+    at = xyz_of(lin, vol)
+    assert np.array_equal(rec["bbox"][:, :3], at) and np.array_equal(rec["bbox"][:, 3:], at)
+    assert np.array_equal(labels.reshape(-1)[lin], np.arange(1, 4097))
+    assert K.labels_per_chunk(labels).tolist() == [2048, 2048]
+
+
+@pytest.mark.parametrize("n", [1023, 1024, 1025, 2048])
+def test_the_first_n_lattice_voxels_of_every_chunk(complib, n):
+    full = K.lattice((64, 16, 16))
+    vol = K.first_n_per_chunk(full, n)
+    assert np.all((vol == 0) | (vol == full)) and (n < 2048 or np.array_equal(vol, full))
+    flat = vol.reshape(-1)
+    for at in (0, K.CHUNK):                                 # the first n of each chunk, not any n
+        assert np.array_equal(np.flatnonzero(flat[at:at + K.CHUNK]), np.flatnonzero(full.reshape(-1)[at:at + K.CHUNK])[:n])
+    labels, rec = comp_ref.label(complib, vol, K.ISO)
+    assert rec["voxels"].size == 2 * n and np.all(rec["voxels"] == 1)
+    assert K.labels_per_chunk(labels).tolist() == [n, n]
+
+
+def test_y_lines_are_two_runs_of_one_component_in_one_chunk(complib):
+    vol = K.y_lines()
+    nz, ny, nx = vol.shape
+    assert nx * ny == K.CHUNK
+    labels, rec = comp_ref.label(complib, vol, K.ISO)
+    assert rec["voxels"].size == 4096 and np.all(rec["voxels"] == 2)
+    bb = rec["bbox"]
+    assert np.all(bb[:, 1] == 0) and np.all(bb[:, 4] == 1) and np.array_equal(bb[:, 0], bb[:, 3]) and np.array_equal(bb[:, 2], bb[:, 5])
+    assert np.all(bb[:, 0] % 2 == 0) and np.all(bb[:, 2] % 2 == 0)
+    assert np.array_equal(labels[:, 0, :], labels[:, 1, :])                   # the two voxels of a column, nx apart
+    per = K.labels_per_chunk(labels)
+    assert per.tolist() == [2048, 0, 2048, 0] and per.max() > K.REC_SLOTS
+
+
+def test_the_odd_lattice_has_chunks_that_cut_rows(complib):
+    vol = K.lattice((13, 11, 120))
+    assert K.CHUNK % 13 != 0
+    labels, rec = comp_ref.label(complib, vol, K.ISO)
+    assert rec["voxels"].size == int((vol == K.ON).sum()) and np.all(rec["voxels"] == 1)
+    assert K.labels_per_chunk(labels).max() > K.REC_SLOTS
+
+
+@pytest.mark.parametrize("stem_from", [0, 6])
+def test_the_lattice_under_a_slab_shares_a_chunk_with_it(complib, stem_from):
+    vol = K.lattice_under_a_slab(stem_from)
+    labels, rec = comp_ref.label(complib, vol, K.ISO)
+    assert rec["voxels"].size == 1536 + 1
+    slab = int(labels[-1, -1, -1])
+    assert rec["voxels"][slab - 1] == 64 * 16 * 14 + 64 * 3 * (10 - stem_from) and np.all(np.delete(rec["voxels"], slab - 1) == 1)
+    assert rec["bbox"][slab - 1].tolist() == [0, 0, stem_from, 63, 15, 23]
+    first = labels.reshape(-1)[:K.CHUNK]
+    assert K.labels_per_chunk(labels)[0] == 1537 and slab in first              # more than a table of them, the slab's among them
+    # labels number the components by first voxel: how many the first chunk holds before the slab's first run
+    assert slab - 1 == 192 * (stem_from + 1)
+    assert (slab - 1 < K.REC_SLOTS) == (stem_from == 0)
+    assert np.unique(labels.reshape(-1)[K.CHUNK:]).tolist() == [0, slab]        # ... and it goes on alone through the next chunks
+
+
+@pytest.mark.parametrize("second_block", [False, True], ids=["one block", "two blocks"])
+def test_a_solid_with_a_hole_has_whole_tiles(complib, second_block):
+    vol = K.solid_with_hole(second_block=second_block)
+    inside = vol == K.ON
+    labels, rec = comp_ref.label(complib, vol, K.ISO)
+    assert rec["voxels"].size == 1 + second_block
+    assert rec["voxels"].tolist() == [int((inside & (labels == c)).sum()) for c in range(1, 2 + second_block)]
+    assert int(rec["voxels"].sum()) == int(inside.sum())
+    assert rec["first_voxel"][0] == 0 and rec["bbox"][0].tolist() == [0, 0, 0, 69, 65, 67]
+    if second_block:
+        assert rec["voxels"][1] == 60 * 52 * 20 and rec["bbox"][1].tolist() == [5, 7, 42, 64, 58, 61]
+        assert K.full_tiles(labels == 1) > 0 and K.full_tiles(labels == 2) == 1 * 6 * 4
+    else:
+        assert rec["voxels"].tolist() == [70 * 66 * 68 - 50 * 20 * 4] == [310160]
+        assert K.full_tiles(inside) == 260
+
+
+def test_full_tiles_counts_aligned_tiles_inside_the_volume():
+    assert K.full_tiles(np.ones((4, 8, 32), dtype=bool)) == 1
+    assert K.full_tiles(np.ones((7, 15, 63), dtype=bool)) == 1 and K.full_tiles(np.ones((3, 8, 32), dtype=bool)) == 0
+    inside = np.ones((8, 16, 64), dtype=bool)
+    assert K.full_tiles(inside) == 8
+    inside[5, 9, 40] = False
+    assert K.full_tiles(inside) == 7
+    shifted = np.zeros((8, 16, 64), dtype=bool)
+    shifted[1:5, 1:9, 1:33] = True                          # a tile's worth, not on the tiles' grid
+    assert K.full_tiles(shifted) == 0
+
+
+def test_no_other_gpu_volume_overfills_a_table_or_fills_a_tile(complib):
+    """What the new volumes are for: of the volumes tests/test_components_gpu.py had before them, none puts more than 1024
+    labels into an 8192-voxel chunk and none holds a whole tile of inside voxels."""
+    vols = []
+    for dtype, isos in ((np.uint8, (40, 128, 220)), (np.uint16, (8000, 30000, 60000))):
+        vol = random_volume((70, 66, 68), dtype, 70 + 66 + 68 + np.dtype(dtype).itemsize)
+        vols += [(vol, comp_ref.iso_stored(iso, dtype, True)) for iso in isos]
+    vols += [(K.nested_shells(), K.ISO), (K.comb()[0], K.ISO)]
+    for vol, iso_s in vols:
+        labels, rec = comp_ref.label(complib, vol, iso_s)
+        assert K.labels_per_chunk(labels).max() <= K.REC_SLOTS
+        assert K.full_tiles(vol.astype(np.float32) >= np.float32(iso_s)) == 0
+
+
 # ---------------------------------------------------------------- the definition's claim about the mesh
 @pytest.mark.parametrize("shape,dtype,iso", RANDOM_CASES, ids=lambda v: getattr(v, "__name__", str(v)))
 def test_every_triangle_belongs_to_one_component_and_removal_removes_rows(complib, meshlib, shape, dtype, iso):

@@ -2,7 +2,8 @@
 (tests/components_ref/components_ref.c), bit for bit as arrays: both voxel types, both layouts, shapes that are no multiple of a
 tile or hold a single voxel; pairs across every kind of tile boundary; a serpentine, a comb, a checkerboard and nested shells;
 the 64-bit parents; the filtered extraction as the restatement's and as the numpy sub-mesh of the device's own full mesh, in one
-piece and in z slabs; and what the labelling does to the handle's state."""
+piece and in z slabs; what the labelling does to the handle's state; chunks with more labels than the records pass's table holds;
+and solid regions, whose whole tiles skip the tile pass's unions."""
 import ctypes as C
 import importlib.util
 from pathlib import Path
@@ -412,3 +413,133 @@ def test_labelling_leaves_the_renderer_alone_and_belongs_to_the_voxels(vra, orac
         assert e.value.code == R.VR_E_INVALID
     finally:
         fresh.close()
+
+
+# ---------------------------------------------------------------- 7. more labels in a chunk than the records' table holds
+WIDTHS = pytest.mark.parametrize("index_bits", [0, 64], ids=["auto", "wide"])
+# name -> (volume, the most labels one 8192-voxel chunk holds; None: more than the table's 1024, however many)
+CROWDED = {
+    "lattice": (lambda: K.lattice((64, 16, 16)), 2048),
+    "first 1023": (lambda: K.first_n_per_chunk(K.lattice((64, 16, 16)), 1023), 1023),       # the table's last slot stays free
+    "first 1024": (lambda: K.first_n_per_chunk(K.lattice((64, 16, 16)), 1024), 1024),       # exactly full, nothing goes direct
+    "first 1025": (lambda: K.first_n_per_chunk(K.lattice((64, 16, 16)), 1025), 1025),       # one label a chunk goes direct
+    "first 2048": (lambda: K.first_n_per_chunk(K.lattice((64, 16, 16)), 2048), 2048),
+    "y lines": (K.y_lines, 2048),                           # two runs a label, the table full between them or before both
+    "odd lattice": (lambda: K.lattice((13, 11, 120)), None),        # chunks cut rows; nx odd: scalar parent stores
+    "slab early": (lambda: K.lattice_under_a_slab(0), 1537),        # a large component in the table, one-voxel ones direct
+    "slab late": (lambda: K.lattice_under_a_slab(6), 1537),         # ... and the large one's runs meeting a full table
+}
+
+
+def label_and_compare(r, complib, key, vol, layout, index_bits, iso=K.ISO, iso_s=K.ISO, most=None, check=None):
+    """the labelling of `vol` on the device against the restatement's; `most`: what the restatement says of the chunks, asserted
+    before the device is asked; `check(labels, rec)`: further conditions on the input"""
+    want = reference(complib, key, vol, iso_s)
+    per = K.labels_per_chunk(want[0])
+    assert per.max() > K.REC_SLOTS if most is None else per.max() == most, per.tolist()
+    if check is not None:
+        check(*want)
+    try:
+        r.setComponentIndexBits(index_bits)
+        r.setLayout(layout)
+        r.setVolume(vol)
+        assert r.labelComponents(iso) == want[1]["voxels"].size
+        assert_same_labelling(r, want, f"{key}, {index_bits}-bit parents")
+    finally:
+        r.setComponentIndexBits(0)
+    return want
+
+
+@WIDTHS
+@LAYOUTS
+@pytest.mark.parametrize("name", sorted(CROWDED))
+def test_chunks_with_more_labels_than_the_table_holds(vra, complib, handle, name, layout, index_bits):
+    make, most = CROWDED[name]
+    vol = make()
+
+    def check(labels, rec):
+        if name.startswith("slab"):                         # the large component shares the crowded chunk
+            slab = int(labels[-1, -1, -1])
+            assert rec["voxels"][slab - 1] > 10000 and slab in labels.reshape(-1)[:K.CHUNK]
+            assert K.labels_per_chunk(labels)[0] > K.REC_SLOTS
+            assert (slab - 1 < K.REC_SLOTS) == (name == "slab early")
+        if name == "y lines":
+            assert np.all(rec["voxels"] == 2) and np.array_equal(labels[:, 0, :], labels[:, 1, :])
+
+    label_and_compare(handle, complib, name, vol, layout, index_bits, most=most, check=check)
+
+
+@LAYOUTS
+def test_a_16_bit_lattice_through_the_offset(vra, complib, handle, layout):
+    r = handle
+    vol = np.where(K.lattice((64, 16, 16)) != 0, 40000, 0).astype(np.uint16)
+    r.setQuirks(vra.renderer.QUIRK_DEFAULT)
+    iso_s = comp_ref.iso_stored(20000, np.uint16, True)
+    assert iso_s == 21000.0
+    label_and_compare(r, complib, "lattice16", vol, layout, 0, iso=20000, iso_s=iso_s, most=2048)
+
+
+# ---------------------------------------------------------------- 8. whole tiles of inside voxels
+def on_off(vol, dtype):
+    """a volume of 0 / K.ON as `dtype`, the iso to label it at and that iso in stored units (16-bit: 0 / 40000 at 20000, which
+    the offset moves to 21000)"""
+    if dtype == np.uint8:
+        return vol.astype(np.uint8), K.ISO, float(K.ISO)
+    return np.where(vol != 0, 40000, 0).astype(np.uint16), 20000, comp_ref.iso_stored(20000, np.uint16, True)
+
+
+@DTYPES
+@WIDTHS
+@LAYOUTS
+@pytest.mark.parametrize("second_block", [False, True], ids=["one block", "two blocks"])
+def test_a_solid_with_a_hole(vra, complib, handle, second_block, layout, index_bits, dtype):
+    r = handle
+    vol, iso, iso_s = on_off(K.solid_with_hole(second_block=second_block), dtype)
+    inside = vol.astype(np.float32) >= np.float32(iso_s)
+    assert K.full_tiles(inside) > 0
+    r.setQuirks(vra.renderer.QUIRK_DEFAULT)
+    r.setMeshWorkspace(0)
+    want = reference(complib, ("solid", second_block, np.dtype(dtype).name), vol, iso_s)
+    assert want[1]["voxels"].size == 1 + second_block
+    for c in range(1, 2 + second_block):                    # whole tiles in every component
+        assert K.full_tiles(want[0] == c) > 0
+    try:
+        r.setComponentIndexBits(index_bits)
+        r.setLayout(layout)
+        r.setVolume(vol)
+        nv, nt = r.extractIsosurface(iso)
+        full = r.readMesh()
+        assert nt > 0 and M.closed_and_oriented(full[2]) == ""
+        assert r.labelComponents(iso) == 1 + second_block
+        assert_same_labelling(r, want, "solid with a hole")
+        assert r.selectComponents(0, 0) == 1 + second_block
+        assert r.extractComponents() == (nv, nt)
+        got = r.readMesh()
+        assert_same_mesh(got, full, "everything selected")
+        assert M.closed_and_oriented(got[2]) == ""
+    finally:
+        r.setComponentIndexBits(0)
+        r.freeMesh()
+
+
+@WIDTHS
+@LAYOUTS
+@pytest.mark.parametrize("shape", [(70, 66, 68), (32, 8, 4)], ids=lambda s: "x".join(map(str, s)))
+def test_a_volume_that_is_all_inside(vra, complib, handle, shape, layout, index_bits):
+    r = handle
+    nx, ny, nz = shape
+    vol = np.full((nz, ny, nx), K.ON, dtype=np.uint8)
+    assert K.full_tiles(vol >= K.ISO) == (nx // 32) * (ny // 8) * (nz // 4) > 0
+    want = reference(complib, ("all inside", shape), vol, K.ISO)
+    assert want[1]["voxels"].tolist() == [vol.size] and want[1]["first_voxel"].tolist() == [0]
+    assert want[1]["bbox"].tolist() == [[0, 0, 0, nx - 1, ny - 1, nz - 1]] and np.all(want[0] == 1)
+    try:
+        r.setComponentIndexBits(index_bits)
+        r.setLayout(layout)
+        r.setVolume(vol)
+        assert r.labelComponents(K.ISO) == 1
+        assert_same_labelling(r, want, "all inside")
+        assert r.extractComponents() == (0, 0)              # no edge crosses the surface
+    finally:
+        r.setComponentIndexBits(0)
+        r.freeMesh()

@@ -178,6 +178,37 @@ def test_the_restatement_is_the_numpy_statement_and_has_the_consequences(simplib
     assert M.same_bits(again, got) == "" and np.array_equal(again_rows, np.arange(got[0].shape[0]))
 
 
+def key_mesh(meshlib, name):
+    if ("keys", name) not in _MESHES:
+        make, iso, spacing = S.KEY_VOLUMES[name]
+        mesh = mesh_ref.extract(meshlib, make(), float(iso), spacing)
+        for a in mesh:
+            a.setflags(write=False)
+        _MESHES[("keys", name)] = mesh
+    return _MESHES[("keys", name)]
+
+
+@pytest.mark.parametrize("name,cell,bits", S.KEY_CASES, ids=S.KEY_CASE_IDS)
+def test_wide_keys_and_empty_axes_are_the_numpy_statement(simplib, meshlib, name, cell, bits):
+    """the cells at which an implementation that packs the three cell indices into one key needs more than 32 bits of it, all 63,
+    or none for one axis.  The numpy statement's fields are 21 bits whatever the extent."""
+    src = key_mesh(meshlib, name)
+    if name.startswith("ties"):
+        assert (src[0].shape[0], src[2].shape[0]) == (162035, 327616)
+    if name == "ties":
+        assert src[0].max(axis=0).tolist() == [39.0, 37.0, 35.0]
+    S.assert_key_case(src[0], name, cell, bits)
+    got, rows = simp_ref.simplify(simplib, src, cell)
+    want, want_rows = S.numpy_simplify(src, cell)
+    problem = M.same_bits(got, want)
+    assert not problem, problem
+    assert np.array_equal(rows, want_rows)
+    assert S.consequences(src, got, rows, cell) == ""
+    if name == "ties":                                      # only coincident vertices share cells this small
+        assert (got[0].shape[0], got[2].shape[0]) == (99298, 220946)
+    assert 0 < got[2].shape[0] < src[2].shape[0]
+
+
 def test_the_ties_volume_has_coincident_vertices_that_resolve_by_index(simplib, meshlib):
     src = source_mesh(meshlib, "ties")
     pos = src[0]

@@ -1,6 +1,7 @@
 """vr_simplify_mesh on the device against its CPU definition (tests/simplify_ref/simplify_ref.c), bit for bit as arrays: the mesh
 the device extracted is read back, simplified by the restatement and compared with what the device made of it -- both voxel
-types, both layouts, a handful of triangles and a million vertices, coincident vertices, smoothed and filtered meshes, repeated
+types, both layouts, a handful of triangles and a million vertices, coincident vertices, cells so small that the packed sort key
+needs up to all of its 63 bits and extents that leave an axis none, smoothed and filtered meshes, repeated
 calls, what the call does to the handle's state, what it refuses, and the files written from its result."""
 import importlib.util
 import struct
@@ -130,6 +131,36 @@ def test_coincident_vertices_resolve_by_index(vra, simplib, handle, cell):
     r.extractIsosurface(100)
     src, got = simplify_and_compare(simplib, r, "ties", cell)
     assert np.unique(src[0], axis=0).shape[0] < src[0].shape[0] - 1000          # the case exists
+
+
+def simplify_a_key_case(vra, simplib, r, layout, name, cell, bits):
+    make, iso, spacing = S.KEY_VOLUMES[name]
+    r.setLayout(layout)
+    r.setQuirks(vra.renderer.QUIRK_DEFAULT)
+    r.setVolume(make(), spacing)
+    nv, nt = r.extractIsosurface(iso)
+    assert nt > 0
+    S.assert_key_case(r.readMesh()[0], name, cell, bits)     # the widths, before the device is asked
+    src, got = simplify_and_compare(simplib, r, ("keys", name), cell)
+    assert 0 < got[2].shape[0] < nt
+    if name == "ties":                                      # only coincident vertices share cells this small
+        assert (nv, nt) == (162035, 327616) and (got[0].shape[0], got[2].shape[0]) == (99298, 220946)
+    assert r.meshInfo() == dict(iso=iso, vertices=got[0].shape[0], triangles=got[2].shape[0])
+
+
+@pytest.mark.parametrize("name,cell,bits", S.KEY_CASES, ids=S.KEY_CASE_IDS)
+def test_keys_wider_than_32_bits_and_axes_without_bits(vra, simplib, handle, name, cell, bits):
+    """the three cell indices are packed into one 64-bit key, each in the bits the extent needs: 36, 39, 57 and all 63 bits of it, three
+    unequal widths, and no bits at all for z or for x.  The 63-bit cell is the largest quotient the call accepts."""
+    simplify_a_key_case(vra, simplib, handle, vra.renderer.LAYOUT_BRICKED, name, cell, bits)
+
+
+LINEAR_KEY_CASES = [S.KEY_CASE_IDS.index("ties, 63 bits"), S.KEY_CASE_IDS.index("flat x, 16 bits")]
+
+
+@pytest.mark.parametrize("at", LINEAR_KEY_CASES, ids=[S.KEY_CASE_IDS[at] for at in LINEAR_KEY_CASES])
+def test_wide_keys_on_the_linear_layout(vra, simplib, handle, at):
+    simplify_a_key_case(vra, simplib, handle, vra.renderer.LAYOUT_LINEAR, *S.KEY_CASES[at])
 
 
 def test_a_smoothed_volume_and_a_filtered_mesh(vra, oracle, simplib, handle):
