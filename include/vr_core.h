@@ -524,6 +524,24 @@ int vr_get_resident_bytes(vr_handle h, uint64_t *volume, uint64_t *copies, uint6
 #define VR_COPY_BUDGET_AUTO UINT64_MAX
 int vr_set_copy_budget(vr_handle h, uint64_t bytes);
 int vr_get_copy_budget(vr_handle h, uint64_t *bytes);
+/* The ray-ordered sample stream of a still view (no reference equivalent; its GUI redraws continuously while only window,
+   alpha and transfer-function sliders move).  Which voxel each sample of a NEAREST frame reads depends on the volume and the
+   ray geometry only, so while camera, image, row range / stripes, volume, step and view switches stand still the voxels the
+   shader's loop reads are kept in device memory in ray order, and frames are rendered by streaming them: every sample is
+   still classified and composited with the frame's own window, alpha, transfer function and MIP setting, and frames are
+   bit-identical to the gather kernels'.  Applies to the frames of the specialised NEAREST kernel with vr_set_skip_empty off.
+   mode 0: never; 1 (default): from the 64th consecutive vr_render* of one geometry on, and never on a launch the measured
+   launch choice wants timed; 2: build at the next eligible launch (tests and tools).  Any change of the geometry or of the
+   rendered voxels makes the stream stale at once.  Building it runs two kernels and BLOCKS the calling thread once on an
+   8-byte read-back (also inside vr_render_async).  The stream -- about 2 bytes (16-bit volumes) per sample of the frame plus
+   padding, 1 GB for a 1024^3 volume at 1920x1080 -- is an optional copy: it counts under `copies` in vr_get_resident_bytes,
+   obeys vr_set_copy_budget (the first copy freed) and is dropped with the voxels.  vr_get_launch_choice is unaffected;
+   vr_get_last_kernel_name reports raymarch_stream_kernel on replayed frames.  Other mode values: VR_E_INVALID. */
+int vr_set_ray_stream(vr_handle h, int mode);
+/* device bytes of the valid stream (samples, per-pixel counts, block offsets); 0: none */
+int vr_get_ray_stream_bytes(vr_handle h, uint64_t *bytes);
+/* how many streams this handle has built so far */
+int vr_get_ray_stream_builds(vr_handle h, uint64_t *builds);
 /* 1-D transfer function (N3): n knots of (iso in 0..255, r,g,b,a); n = 0 restores the
    reference grey ramp.  Built with the natural cubic spline of src/CubicSpline.cpp. */
 int vr_set_transfer_function(vr_handle h, const int32_t *iso, const float *rgba4, int n);

@@ -3,6 +3,8 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
+#include <cstring>
 
 #include "launch_tuner.h"
 #include "tile_schedule.h"
@@ -166,6 +168,36 @@ int launchCandidates(const FrameParams &P, const LaunchConfig &L, int prior, int
         }
     }
     return n;
+}
+
+bool RayGeometryKey::operator==(const RayGeometryKey &o) const { return std::memcmp(w, o.w, sizeof(w)) == 0; }
+
+RayGeometryKey rayGeometryKey(const FrameParams &P, const LaunchConfig &L, uint64_t volume_generation)
+{
+    RayGeometryKey k;
+    int n = 0;
+    auto put = [&](const void *p, int words) { std::memcpy(k.w + n, p, sizeof(uint32_t) * (size_t)words); n += words; };
+    static_assert(sizeof(float) == 4 && sizeof(int32_t) == 4, "the key is words");
+    put(P.cam, 21);
+    put(&P.img_w, 1); put(&P.img_h, 1);
+    put(&P.row_begin, 1); put(&P.row_end, 1);
+    put(&P.col_lim, 1); put(&P.row_lim, 1);
+    put(&P.stripe_rows, 1); put(&P.stripe_index, 1); put(&P.stripe_count, 1);
+    put(&P.nx, 1); put(&P.ny, 1); put(&P.nz, 1);
+    put(P.half, 3); put(P.pmin, 3); put(P.pmax, 3); put(P.ext, 3); put(P.rext, 3);
+    put(&P.step, 1);
+    put(&P.max_steps, 1);
+    put(&P.view_top, 1); put(&P.view_bottom, 1);
+    const int32_t cfg[3] = {L.divmode_tc, L.layout, L.bytes_per_voxel};
+    put(cfg, 3);
+    put(&volume_generation, 2);
+    if (n != RayGeometryKey::kWords) std::abort();                      // (launch_plan.h: kWords)
+    return k;
+}
+
+bool rayStreamEligible(const FrameParams &P, const LaunchConfig &L, int skip_empty_switch)
+{
+    return fast_path_eligible(P, L) && L.tile_table != nullptr && skip_empty_switch == 0;
 }
 
 // threshold: largest voxel value whose classification is exactly zero

@@ -50,6 +50,24 @@ void applyChoice(LaunchConfig &L, int bits);
 constexpr int kMaxCandidates = 8;            // == LaunchTuner::kTuneCand (launch_plan.cpp asserts it)
 int launchCandidates(const FrameParams &P, const LaunchConfig &L, int prior, int out[kMaxCandidates]);
 
+// The ray-ordered sample stream (vr_stream.hip) holds the voxels the shader's loop reads; it stays valid exactly while this key
+// stays the same, bit for bit: everything that determines WHICH voxel each sample of this launch reads -- the camera block, the
+// image and the rows / stripes / Q1 limits of the launch, the volume's dimensions and box, the step and its cap, the view
+// switches, the texcoord division, layout and voxel type -- and the generation of the resident voxels (RendererCore counts
+// every writer of its volume).  NOT in the key, so that they render from the same stream: window, alpha, transfer function,
+// MIP's compositing (its step is), the target's pointer / format / compactness, the packed copy, the tuner's variant bits.
+struct RayGeometryKey {
+    static constexpr int kWords = 57;
+    uint32_t w[kWords];
+    bool operator==(const RayGeometryKey &o) const;
+    bool operator!=(const RayGeometryKey &o) const { return !(*this == o); }
+};
+RayGeometryKey rayGeometryKey(const FrameParams &P, const LaunchConfig &L, uint64_t volume_generation);
+// may this launch be replayed from a stream at all: the fast kernel's frames, a tile table to walk, skipping not switched on
+bool rayStreamEligible(const FrameParams &P, const LaunchConfig &L, int skip_empty_switch);
+// default mode (vr_set_ray_stream 1): replay starts with this many consecutive launches of one geometry
+constexpr int kRayStreamStillLaunches = 64;
+
 // the largest stored value every sample at or below which classifies to alpha exactly 0 (composite mode; the window min_val ..
 // max_val, tf_lut: 256 x RGBA or nullptr = grey ramp, P.alpha_scale); whole_run: the table's whole leading zero-alpha run must
 // lie beyond it (TRILINEAR, whose values fall between the integers).  false: even the lowest value is visible

@@ -24,6 +24,7 @@
 #include "vr_mesh.h"
 #include "vr_simplify.h"
 #include "vr_kernels.h"
+#include "vr_stream.h"
 
 namespace vr {
 
@@ -157,6 +158,7 @@ bool RendererCore::loadShader(std::string fn, bool reload)
         check(launch_warm_mesh(stream()), "module pre-load (extraction)");
         check(launch_warm_components(stream()), "module pre-load (components)");
         check(launch_warm_simplify(stream()), "module pre-load (simplification)");
+        check(launch_warm_stream(stream()), "module pre-load (sample stream)");
         check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
         tslab_warm_ = false;
         if (filter == 1) warmTrilinear();
@@ -209,6 +211,9 @@ void RendererCore::dropDerived()
 {
     tiles_.invalidateSkipOrder();                                        // (an order built on the old volume's visibility)
     copies_.dropAll();
+    volume_generation_++;                                                // new voxels: no ray-ordered sample stream of the old ones is this volume's
+    still_key_valid_ = false;
+    still_launches_ = 0;
 }
 
 DeviceBuffer<uint8_t> RendererCore::allocVolumeBuffer(int nx, int ny, int nz, int bytes, int lay)
@@ -753,7 +758,47 @@ RendererCore::PreparedLaunch RendererCore::prepareLaunch()
     // the specialised kernels gather from the packed copy when their address tables fit (vr_kernels.hip: dispatch_fast3)
     last_packed12_bytes_ = (L.packed12 && P.nx + P.ny + P.nz <= 3072) ? (size_t)L.packed12_bytes : 0;
     tuneChoose(F);
+    F.stream_eligible = rayStreamEligible(P, L, skip_empty);
+    if (F.stream_eligible) F.stream_key = rayGeometryKey(P, L, volume_generation_);
     return F;
+}
+
+void RendererCore::setRayStream(int mode)
+{
+    if (mode < 0 || mode > 2) throw std::invalid_argument("setRayStream: unknown mode");
+    ray_stream_mode_ = mode;                                             // (0 keeps a valid stream: it is used again if the geometry still stands when the mode returns)
+}
+
+// The ray-ordered sample stream (vr_stream.hip): counts this launch's geometry and decides whether the launch replays.  A launch
+// that cannot replay (another mode or filter, skipping, no tile table) or whose geometry differs from the last one's makes the
+// stream stale at once; its allocation is kept for the next build.  Mode 1: replay from the kRayStreamStillLaunches-th
+// consecutive launch of one geometry on, and not on a launch the measured choice wants timed or tried -- that launch runs the
+// gather kernel it asks for, and the count goes on; a forced kernel variant (vr_set_kernel_variant) runs that kernel.  Mode 2:
+// the next eligible launch builds.  A countSamples launch counts but neither builds nor replays.  The build
+// (VolumeCopies::ensureRayStream) blocks on one 8-byte read-back; it happens here, before render()'s timed stretch.  A camera
+// that moves every frame pays the key comparison and nothing else.
+void RendererCore::engageRayStream(PreparedLaunch &F, const uint32_t *spp)
+{
+    F.replay = false;
+    if (!F.stream_eligible) {
+        still_key_valid_ = false;
+        still_launches_ = 0;
+        copies_.invalidateRayStream();
+        return;
+    }
+    if (still_key_valid_ && F.stream_key == still_key_) {
+        still_launches_++;
+    } else {
+        still_key_ = F.stream_key;
+        still_key_valid_ = true;
+        still_launches_ = 1;
+        copies_.invalidateRayStream();
+    }
+    if (spp != nullptr) return;
+    const bool wanted = ray_stream_mode_ == 2 ||
+                        (ray_stream_mode_ == 1 && force_generic == 0 && still_launches_ >= kRayStreamStillLaunches && !F.pick.measure && !F.pick.trial);
+    if (!wanted) return;
+    F.replay = copies_.ensureRayStream(residentVolume(), F.P, F.L);
 }
 
 // the LDS-staged TRILINEAR kernel's seven code objects (vr_tslab.hip), loaded when TRILINEAR is selected -- vr_set_filter,
@@ -775,9 +820,10 @@ void RendererCore::warmTrilinear()
 // (tuneCollect) -- and a countSamples launch never measures
 void RendererCore::launch(uint32_t *spp, bool blocking)
 {
-    const PreparedLaunch F = prepareLaunch();
+    PreparedLaunch F = prepareLaunch();
+    engageRayStream(F, spp);
     const LaunchTuner::Pick &pick = F.pick;
-    const bool measure = pick.measure && spp == nullptr && (blocking || tune_count_ < kTuneSlots);
+    const bool measure = pick.measure && !F.replay && spp == nullptr && (blocking || tune_count_ < kTuneSlots);   // (a forced replay is no measurement of the gather kernel)
     TuneSlot &slot = tune_slot_[(tune_head_ + tune_count_) % kTuneSlots];
     const hipEvent_t e0 = blocking ? ev0_ : slot.ev0, e1 = blocking ? ev1_ : slot.ev1;
     if (blocking || measure) check(hipEventRecord(e0, stream()), "hipEventRecord");
@@ -1023,6 +1069,7 @@ hipError_t RendererCore::launchKernel(const PreparedLaunch &F, uint32_t *spp)
     }
     case FrameMode::RayMarch: break;
     }
+    if (F.replay && spp == nullptr) return launch_raymarch_stream(P, L, d_tf_.get(), F.fb, copies_.rayStream(), stream(), &last_kernel_);
     return launch_raymarch(P, L, d_vol_.get(), d_tf_.get(), F.fb, spp, stream(), &last_kernel_);
 }
 

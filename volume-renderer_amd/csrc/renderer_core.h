@@ -15,6 +15,7 @@
 
 #include "camera.h"
 #include "device_buffer.h"
+#include "launch_plan.h"
 #include "launch_tuner.h"
 #include "tile_tables.h"
 #include "volume_copies.h"
@@ -118,6 +119,16 @@ public:
     static constexpr uint64_t kCopyBudgetAuto = VolumeCopies::kBudgetAuto;
     void setCopyBudget(uint64_t bytes);
     uint64_t copyBudget() const { return copies_.budget(); }
+    // The ray-ordered sample stream of a still view (vr_set_ray_stream; vr_stream.hip): NEAREST frames of the
+    // fast kernel's modes, with skipping off, are replayed from a copy of the voxels their samples read while the ray geometry
+    // (launch_plan.h: rayGeometryKey) stands still.  0 off; 1 automatic: from the 64th consecutive launch of one geometry on,
+    // and never on a launch the measured choice wants timed or tried; 2 build at the next eligible launch.  Frames are the same
+    // bits either way.  Building blocks once on an 8-byte read-back; the stream counts as a copy (residentBytes, setCopyBudget).
+    void setRayStream(int mode);
+    int rayStreamMode() const { return ray_stream_mode_; }
+    uint64_t rayStreamBytes() const { return copies_.rayStreamBytes(); }
+    uint64_t rayStreamElements() const { return copies_.rayStreamElements(); }
+    uint64_t rayStreamBuilds() const { return copies_.rayStreamBuilds(); }
     bool hasDevice() const { return device_ >= 0; }
     void warmTrilinear();                    // pre-load the staged TRILINEAR kernel's code objects (once)
     // first-hit isosurface mode (vr_set_isosurface): while on, frames are the shaded surface and its depth, whatever the MIP /
@@ -305,7 +316,16 @@ private:
         const uint16_t *skip_grid = nullptr; // the isosurface and the shaded kernel: the grid they skip on (nullptr = no skipping) ...
         int skip_thresh = 0;                 // ... and the shaded kernel's threshold (the ray-march kernels carry theirs in P and L)
         LaunchTuner::Pick pick;              // the tuner's decision (measure: the launch is a measurement)
+        bool stream_eligible = false;        // a frame the ray-ordered sample stream could replay (rayStreamEligible) ...
+        RayGeometryKey stream_key;           // ... and its geometry
+        bool replay = false;                 // engageRayStream: this launch reads the stream
     };
+    int ray_stream_mode_ = 1;
+    uint64_t volume_generation_ = 0;         // counts the writers of d_vol_ (dropDerived)
+    bool still_key_valid_ = false;
+    RayGeometryKey still_key_;               // the geometry of the last eligible launch ...
+    int still_launches_ = 0;                 // ... and how many consecutive launches have had it
+    void engageRayStream(PreparedLaunch &F, const uint32_t *spp);   // counts the launch; builds / selects the stream by the mode's rule
     hipError_t launchKernel(const PreparedLaunch &F, uint32_t *spp);   // the ray-march, the iso, the reslice or the shaded kernel
     TileTables tiles_;                       // the work-ordered block -> tile tables the specialised kernels walk
     const char *last_kernel_ = "";

@@ -27,12 +27,14 @@ void VolumeCopies::dropAll()
 {
     for (auto *q : {&vol12_, &apron_, &apron_perm_[0], &apron_perm_[1]}) q->reset();
     skip_grid_.reset();
+    dropRayStream();
     rearm();
 }
 
 void VolumeCopies::trimToBudget(hipStream_t stream)
 {
     if (copiesBytes() > budget_) hipCheck(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    if (copiesBytes() > budget_) dropRayStream();                       // (the cheapest to build again)
     if (copiesBytes() > budget_) for (auto &q : apron_perm_) q.reset();
     if (copiesBytes() > budget_) apron_.reset();
     if (copiesBytes() > budget_) vol12_.reset();
@@ -81,6 +83,46 @@ bool VolumeCopies::ensureApronPerm(const ResidentVolume &V, uint64_t bytes)
     if (apron_perm_failed_)                                             // one without the other is 1.25 volumes of dead memory, in the low-memory case
         for (auto &q : apron_perm_) q.reset();
     return hasApronPerm();
+}
+
+bool VolumeCopies::ensureRayStream(const ResidentVolume &V, const FrameParams &P, const LaunchConfig &L)
+{
+    if (stream_valid_ || stream_failed_) return stream_valid_;
+    const StreamGrid g = streamGrid(P.img_w, launch_local_rows(P));
+    if (g.blocks == 0) return false;
+    auto refuse = [&]() { dropRayStream(); stream_failed_ = true; return false; };
+    // the small arrays: n per pixel, the blocks' offsets (kept from an earlier build where they are large enough)
+    const size_t n_counts = (size_t)g.blocks * 64u, n_offsets = (size_t)g.blocks + 1u;
+    if (stream_counts_.size() < n_counts || stream_offsets_.size() < n_offsets) {
+        dropRayStream();
+        if (!copyFits(n_counts * 2u + n_offsets * 8u) || !stream_counts_.tryAlloc(n_counts) || !stream_offsets_.tryAlloc(n_offsets)) return refuse();
+    }
+    uint64_t total = 0;
+    {
+        DeviceBuffer<uint32_t> block_elems;
+        if (!block_elems.tryAlloc(g.blocks)) return refuse();
+        hipError_t e = launch_stream_count(P, L, stream_counts_.get(), block_elems.get(), V.stream);
+        if (e == hipSuccess) e = launch_stream_scan(block_elems.get(), stream_offsets_.get(), g.blocks, V.stream);
+        // the stream's length: the one blocking read-back of a build
+        if (e == hipSuccess) e = hipMemcpyAsync(&total, stream_offsets_.get() + g.blocks, sizeof(total), hipMemcpyDeviceToHost, V.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(V.stream);
+        if (e != hipSuccess) dropRayStream();
+        hipCheck(e, "stream_record_kernel (count)");
+    }
+    const uint64_t bytes = total * (uint64_t)V.bytes_per_voxel + 16u;
+    if (stream_samples_.bytes() < bytes) {
+        stream_samples_.reset();                                         // (before the question whether the new one fits)
+        if (!copyFits(bytes) || !stream_samples_.tryAlloc(bytes)) return refuse();
+    }
+    hipError_t e = hipSuccess;
+    if (total != 0) e = launch_stream_record(P, L, V.data, stream_counts_.get(), stream_offsets_.get(), stream_samples_.get(), V.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(V.stream);
+    if (e != hipSuccess) dropRayStream();
+    hipCheck(e, "stream_record_kernel");
+    stream_elements_ = total;
+    stream_valid_ = true;
+    stream_builds_++;
+    return true;
 }
 
 void VolumeCopies::ensureSkipGrid(const ResidentVolume &V, size_t cells)

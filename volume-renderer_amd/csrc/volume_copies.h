@@ -1,10 +1,11 @@
 // volume_copies.h -- what RendererCore builds lazily from the voxels of the volume it renders and drops with them: the optional
 // speed copies (12-bit packed copy, TRILINEAR's apron copy and its two per-axis permutations), bounded by the copy budget, and
-// the skip grid.  WHEN each is wanted is RendererCore's policy (refreshPacked12 / refreshApron / ensureSkipGrid); this class
+// the skip grid -- and the ray-ordered sample stream of a still view (vr_stream.hip), which also depends on the ray geometry.  WHEN each is wanted is RendererCore's policy (refreshPacked12 / refreshApron / ensureSkipGrid); this class
 // allocates, runs the build kernel, synchronises, frees on error and remembers a refusal.
 #pragma once
 #include "device_buffer.h"
 #include "vr_frame.h"
+#include "vr_stream.h"
 
 namespace vr {
 
@@ -28,11 +29,21 @@ public:
     bool ensureApron(const ResidentVolume &V, uint64_t bytes);
     bool ensureApronPerm(const ResidentVolume &V, uint64_t bytes);   // both per-axis copies or none
     void ensureSkipGrid(const ResidentVolume &V, size_t cells);
+    // The ray-ordered sample stream of the launch (P, L): samples, per-pixel counts and block offsets.  true = valid for this
+    // geometry (built now if it was not: count pass, scan, ONE blocking 8-byte read-back of the total, record pass).  false =
+    // refused like a copy.  invalidateRayStream: the geometry changed -- stale at once, the allocation is kept for the next build.
+    bool ensureRayStream(const ResidentVolume &V, const FrameParams &P, const LaunchConfig &L);
+    void invalidateRayStream() { stream_valid_ = false; }
+    bool rayStreamValid() const { return stream_valid_; }
+    RayStreamView rayStream() const { return {stream_samples_.get(), stream_counts_.get(), stream_offsets_.get()}; }
+    uint64_t rayStreamBytes() const { return stream_valid_ ? rayStreamAllocated() : 0; }   // what a replayed frame holds resident
+    uint64_t rayStreamElements() const { return stream_valid_ ? stream_elements_ : 0; }    // samples incl. padding
+    uint64_t rayStreamBuilds() const { return stream_builds_; }
     void dropAll();
     void setBudget(uint64_t bytes) { budget_ = bytes; rearm(); }   // a new budget re-arms what an old one refused; frees nothing
     void trimToBudget(hipStream_t stream);   // over the budget: drop copies, the least valuable first (per-axis aprons, apron, packed copy)
     uint64_t budget() const { return budget_; }
-    uint64_t copiesBytes() const { return vol12_.bytes() + apron_.bytes() + apron_perm_[0].bytes() + apron_perm_[1].bytes(); }   // optional copies resident now
+    uint64_t copiesBytes() const { return vol12_.bytes() + apron_.bytes() + apron_perm_[0].bytes() + apron_perm_[1].bytes() + rayStreamAllocated(); }   // optional copies resident now
     bool copyFits(uint64_t bytes) const;     // may another optional copy of `bytes` be allocated (budget / free device memory)?
     const void *packed12() const { return vol12_.get(); }
     size_t packed12Bytes() const { return vol12_.bytes() - 16; }   // (every copy ends in 16 zeroed bytes of slack)
@@ -46,7 +57,9 @@ public:
     unsigned skipGridMin() const { return skip_grid_min_; }         // smallest cell value of the grid (read back once when it is built)
 
 private:
-    void rearm() { vol12_failed_ = apron_failed_ = apron_perm_failed_ = false; }
+    void rearm() { vol12_failed_ = apron_failed_ = apron_perm_failed_ = stream_failed_ = false; }
+    uint64_t rayStreamAllocated() const { return stream_samples_.bytes() + stream_counts_.bytes() + stream_offsets_.bytes(); }
+    void dropRayStream() { stream_samples_.reset(); stream_counts_.reset(); stream_offsets_.reset(); stream_valid_ = false; stream_elements_ = 0; }
     bool buildApron(const ResidentVolume &V, DeviceBuffer<uint8_t> &d, uint64_t bytes, int order);
     DeviceBuffer<uint8_t> vol12_, apron_, apron_perm_[2];
     bool vol12_failed_ = false, apron_failed_ = false, apron_perm_failed_ = false;   // refused for this volume and budget: do not retry
@@ -54,6 +67,11 @@ private:
     uint64_t budget_ = kBudgetAuto;
     DeviceBuffer<uint16_t> skip_grid_;       // dilated cell-max grid
     unsigned skip_grid_min_ = 0;
+    DeviceBuffer<uint8_t> stream_samples_;   // the ray-ordered sample stream (+ 16 bytes of slack)
+    DeviceBuffer<uint16_t> stream_counts_;
+    DeviceBuffer<uint64_t> stream_offsets_;
+    bool stream_valid_ = false, stream_failed_ = false;
+    uint64_t stream_elements_ = 0, stream_builds_ = 0;
 };
 
 }  // namespace vr

@@ -561,6 +561,27 @@ int vr_set_copy_budget(vr_handle h, uint64_t bytes)
     return guarded(h, [&](vr::RendererCore &c) { c.setCopyBudget(bytes); });
 }
 
+int vr_set_ray_stream(vr_handle h, int mode)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.setRayStream(mode); });
+}
+
+int vr_get_ray_stream_bytes(vr_handle h, uint64_t *bytes)
+{
+    return guarded(h, [&](vr::RendererCore &c) {
+        if (!bytes) throw std::invalid_argument("vr_get_ray_stream_bytes: null result");
+        *bytes = c.rayStreamBytes();
+    });
+}
+
+int vr_get_ray_stream_builds(vr_handle h, uint64_t *builds)
+{
+    return guarded(h, [&](vr::RendererCore &c) {
+        if (!builds) throw std::invalid_argument("vr_get_ray_stream_builds: null result");
+        *builds = c.rayStreamBuilds();
+    });
+}
+
 int vr_get_copy_budget(vr_handle h, uint64_t *bytes)
 {
     return guarded(h, [&](vr::RendererCore &c) {

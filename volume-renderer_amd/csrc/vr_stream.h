@@ -1,0 +1,44 @@
+// vr_stream.h -- host-callable launchers of vr_stream.hip: the ray-ordered sample stream of a still view (vr_set_ray_stream)
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "tile_schedule.h"
+#include "vr_frame.h"
+
+namespace vr {
+
+// The stream's blocks are the 8x8-pixel wavefront tiles of the fast kernel's 32x16-pixel workgroup tiles: 4 x 2 of them per
+// tile, whole tiles even where the image ends inside one (their lanes outside the image hold no sample).
+constexpr unsigned kStreamGroup = 4;          // G: samples a lane reads with one load
+struct StreamGrid { unsigned blocks_x, blocks_y, blocks; };
+inline StreamGrid streamGrid(int img_w, int rows)
+{
+    StreamGrid g;
+    g.blocks_x = (unsigned)((img_w + (int)kFastTileW - 1) / (int)kFastTileW) * (kFastTileW / 8u);
+    g.blocks_y = (unsigned)((rows + (int)kFastTileH - 1) / (int)kFastTileH) * (kFastTileH / 8u);
+    g.blocks = g.blocks_x * g.blocks_y;
+    return g;
+}
+
+// what a replayed frame reads (device pointers; VolumeCopies owns them)
+struct RayStreamView {
+    const void *samples;          // VoxelT: sample i of lane l of block b at offsets[b] + (i / G) * 64 * G + l * G + i % G
+    const uint16_t *counts;       // n per pixel, blocks * 64 (lane-major inside a block)
+    const uint64_t *offsets;      // blocks + 1 element offsets; the last is the stream's length
+};
+
+// pass 1: the geometric sample count n of every ray into counts[blocks * 64] and n_max(block) * 64 -- n_max rounded up to G --
+// into block_elems[blocks]
+hipError_t launch_stream_count(const FrameParams &P, const LaunchConfig &L, uint16_t *counts, uint32_t *block_elems, hipStream_t st);
+// exclusive scan of block_elems into offsets[blocks + 1] (64-bit element offsets; offsets[blocks] = the total)
+hipError_t launch_stream_scan(const uint32_t *block_elems, uint64_t *offsets, unsigned blocks, hipStream_t st);
+// pass 2: the raw voxel of sample i of every ray into the stream (a padded slot holds voxel (0, 0, 0))
+hipError_t launch_stream_record(const FrameParams &P, const LaunchConfig &L, const void *vol, const uint16_t *counts,
+                                const uint64_t *offsets, void *samples, hipStream_t st);
+// a frame from the stream: classification and compositing of every recorded sample (the fast kernel's modes; needs L.tile_table)
+hipError_t launch_raymarch_stream(const FrameParams &P, const LaunchConfig &L, const float4 *tf, float4 *fb, const RayStreamView &S,
+                                  hipStream_t st, const char **kernel_name);
+hipError_t launch_warm_stream(hipStream_t st);   // one empty launch per translation unit of vr_stream.hip
+
+}  // namespace vr

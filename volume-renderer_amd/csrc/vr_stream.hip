@@ -1,0 +1,489 @@
+// vr_stream.hip -- the ray-ordered sample stream of a still view (vr_set_ray_stream).
+//
+// Which voxel each sample of a NEAREST frame reads depends on the volume and the ray geometry only -- not on the window, the
+// opacity scale, the transfer function or MIP.  While the geometry stands still (RendererCore: rayGeometryKey), the voxels the
+// shader's loop reads are kept in HBM in ray order, and a frame is rendered by streaming them: one coalesced load per lane per
+// G = 4 samples, then classification and compositing with the shader's own operations in the shader's order.  Another speed
+// copy that holds the same voxels (like the 12-bit packed copy): frames are bit-identical, and every replayed frame still
+// classifies and composites every sample, so window, alpha, transfer-function and MIP changes render from the same stream.
+//
+// Build (once per still view; VolumeCopies::ensureRayStream): stream_record_kernel<COUNT> writes the geometric sample count n
+// of every ray, a device scan turns the blocks' padded lengths into 64-bit element offsets, the host reads the total back --
+// ONE blocking 8-byte read-back per build -- allocates, and stream_record_kernel<!COUNT> writes the voxels.
+// Layout: a block is one 8x8-pixel wavefront tile; n_max(block) = max n over its lanes rounded up to G; sample i of lane l sits
+// at offsets[block] + (i / G) * 64 * G + l * G + i % G: a wavefront instruction reads 512 (u16) / 256 (u8) contiguous bytes.
+//
+// Its own translation units (VR_STREAM_TU = 0: 8-bit volumes, the scan and the entry points; 1: 16-bit volumes), like
+// vr_iso.hip: the vr_kernels.hip units are untouched, a frame whose camera moves runs the machine code it always ran.  Shared
+// with them is what vr_device.h offers; the classification table, classify and accumulate are restated from vr_fast.hip, each
+// with the shader lines it implements.  Arithmetic contract as in vr_kernels.hip (-ffp-contract=off, one rounding per step).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "vr_device.h"
+#include "vr_lds_dma.h"
+#include "vr_stream.h"
+
+#ifndef VR_STREAM_TU
+#define VR_STREAM_TU -1
+#endif
+// groups of G samples a lane keeps in flight beyond the ones it composites, and plain (0) or non-temporal (1) stream loads:
+// measured alternatives in docs/lab-notebook.md, "Ray-ordered sample stream: first measurements"
+#ifndef VR_STREAM_DEPTH
+#define VR_STREAM_DEPTH 4
+#endif
+#ifndef VR_STREAM_NT
+#define VR_STREAM_NT 1
+#endif
+
+namespace vr {
+
+constexpr unsigned STREAM_G = kStreamGroup, STREAM_BLOCK_ELEMS = 64u * STREAM_G;
+static_assert(STREAM_G == 4, "a group is one 8-byte (u16) / 4-byte (u8) load: the packing below spells out four samples");
+
+// ------------------------------------------------------------------ build: count / record
+// One pixel per lane, 8x8 pixels per wavefront (= one stream block), four blocks per workgroup, over the launch's local rows:
+// stripes, compact targets and the Q1 limits as raymarch_fast_kernel maps them (vr_fast.hip:80-91).  The shader's loop,
+// literally: position mapping, bounds test and clamped voxel index of checked_step (vr_fast.hip:393-410) -- with no opacity
+// test and no compositing.  COUNT: n = iterations until a bound test fails (<= max_steps, fits 16 bits).  !COUNT: the same
+// positions once more, the bound tests replaced by i < n of the count pass, the fetches of 8 samples issued together (the
+// positions do not depend on the data); always from the resident volume, never from the packed copy.
+template <typename VoxelT, int LAYOUT, bool BIG, bool COUNT>
+__global__ __launch_bounds__(256) void stream_record_kernel(const FrameParams P, const int divmode, const int view,
+                                                            const VoxelT *__restrict__ vol, const uint32_t vol_bytes,
+                                                            uint16_t *__restrict__ counts, uint32_t *__restrict__ block_elems,
+                                                            const uint64_t *__restrict__ offsets, VoxelT *__restrict__ samples,
+                                                            const unsigned blocks_x, const unsigned blocks)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned sb = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+    if (sb >= blocks) return;
+    const unsigned bx = sb % blocks_x, by = sb / blocks_x;
+    const int lx = (int)(bx * 8u + (lane & 7u)), ly = (int)(by * 8u + (lane >> 3));
+    const int px = lx;
+    int py;
+    if (P.stripe_count > 1) {
+        const int s = ly / P.stripe_rows, r = ly % P.stripe_rows;
+        py = (s * P.stripe_count + P.stripe_index) * P.stripe_rows + r;
+    } else {
+        py = P.row_begin + ly;
+    }
+    const bool in_image = !(px >= P.col_lim || py >= P.row_lim || py >= P.row_end);
+
+    Ray ray = {};
+    float t_min = 0.0f, t_max = 0.0f;
+    bool hit = false;
+    if (in_image) {
+        ray = compute_ray(P, (float)px + 0.5f, (float)py + 0.5f);
+        hit = intersect_ray_aabb(P, ray, t_min, t_max);
+    }
+    const float EPSILON = 0.000001f;
+    const float sx = ray.ox + ray.dx * t_min, sy = ray.oy + ray.dy * t_min, sz = ray.oz + ray.dz * t_min;
+    float x = sx + ray.dx * EPSILON, y = sy + ray.dy * EPSILON, z = sz + ray.dz * EPSILON;
+    const float dsx = ray.dx * P.step, dsy = ray.dy * P.step, dsz = ray.dz * P.step;
+    // cartesianToTextureCoord (VolumeRenderer.cs:175-192) as checked_step restates it; the division by run-time mode
+    // (DIV_UNIT: the divisor is exactly 1; DIV_CERT: the certified quotient) -- a wave-uniform switch in a one-off kernel
+    auto texcoord = [&](float ax, float ay, float az, float &tcx, float &tcy, float &tcz) {
+        float ux = ax + P.half[0], uy = ay + P.half[1], uzr = az + P.half[2];   // z before the flip of :185
+        if (divmode == DIV_CERT) {
+            ux = div_cert(ux, P.ext[0], P.rext[0]);
+            uy = div_cert(uy, P.ext[1], P.rext[1]);
+            uzr = div_cert(uzr, P.ext[2], P.rext[2]);
+        }
+        const float uz = 1.0f - uzr;
+        tcx = ux; tcy = uy; tcz = uz;
+        if (view == 1) { tcy = uzr; tcz = uy; }                 // view_top
+        else if (view == 2) { tcy = uz; tcz = 1.0f - uy; }      // view_bottom
+    };
+
+    if constexpr (COUNT) {
+        int n = 0;
+        if (hit) {
+            for (; n < P.max_steps; n++) {
+                float tcx, tcy, tcz;
+                texcoord(x, y, z, tcx, tcy, tcz);
+                if (tcx > 1.0f || tcy > 1.0f || tcz > 1.0f || tcx < 0.0f || tcy < 0.0f || tcz < 0.0f) break;
+                x += dsx; y += dsy; z += dsz;
+            }
+        }
+        counts[(size_t)sb * 64u + lane] = (uint16_t)n;
+        int nmax = n;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) nmax = max(nmax, __shfl_xor(nmax, d, 64));
+        if (lane == 0) block_elems[sb] = (((uint32_t)nmax + STREAM_G - 1u) / STREAM_G) * STREAM_BLOCK_ELEMS;
+    } else {
+        const int n = (int)counts[(size_t)sb * 64u + lane];
+        const uint64_t off = offsets[sb];
+        const uint32_t ngroups = (uint32_t)((offsets[sb + 1] - off) / STREAM_BLOCK_ELEMS);
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)vol, 0, BIG ? 0 : (int)vol_bytes, 0x00020000);
+        using GroupT = typename std::conditional<sizeof(VoxelT) == 2, uint2, uint32_t>::type;
+        GroupT *out = reinterpret_cast<GroupT *>(samples + off) + lane;
+        for (uint32_t g = 0; g < ngroups; g += 2) {
+            typename VoxelAddr<LAYOUT, BIG>::type a[8];
+            bool live[8];
+            uint32_t t[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                live[u] = (int)(g * STREAM_G) + u < n;
+                float tcx, tcy, tcz;
+                texcoord(x, y, z, tcx, tcy, tcz);
+                // (the count pass proved tc >= 0 for the live samples; the lower clamp only keeps a lane past its n inside the volume)
+                const int vi = max(min((int)(tcx * P.fdim[0]), P.nx - 1), 0);
+                const int vj = max(min((int)(tcy * P.fdim[1]), P.ny - 1), 0);
+                const int vk = max(min((int)(tcz * P.fdim[2]), P.nz - 1), 0);
+                a[u] = VoxelAddr<LAYOUT, BIG>::at(P, vi, vj, vk);
+                // a padded slot holds voxel (0, 0, 0): a value of the volume (the replay classifies whole groups, and never composites it)
+                if (!live[u]) a[u] = 0;
+                x += dsx; y += dsy; z += dsz;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; u++) t[u] = VoxelFetch<VoxelT, BIG>::load(vol, rs, a[u]);
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                if (g + (uint32_t)h >= ngroups) break;
+                const uint32_t *q = t + 4 * h;
+                if constexpr (sizeof(VoxelT) == 2) out[(size_t)(g + h) * 64u] = make_uint2(q[0] | (q[1] << 16), q[2] | (q[3] << 16));
+                else out[(size_t)(g + h) * 64u] = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
+            }
+        }
+    }
+}
+
+template <typename VoxelT, int LAYOUT, bool BIG>
+static hipError_t launch_record_instance(const FrameParams &P, const LaunchConfig &L, const void *vol, uint16_t *counts,
+                                         uint32_t *block_elems, const uint64_t *offsets, void *samples, hipStream_t st)
+{
+    const int rows = launch_local_rows(P);
+    if (rows <= 0 || P.img_w <= 0) return hipSuccess;
+    const StreamGrid g = streamGrid(P.img_w, rows);
+    const int view = P.view_top == 1 ? 1 : (P.view_bottom == 1 ? 2 : 0);
+    const dim3 grid((g.blocks + 3u) / 4u), block(256);
+    if (samples == nullptr)
+        hipLaunchKernelGGL((stream_record_kernel<VoxelT, LAYOUT, BIG, true>), grid, block, 0, st, P, L.divmode_tc, view, (const VoxelT *)vol,
+                           (uint32_t)L.vol_bytes32, counts, block_elems, offsets, (VoxelT *)nullptr, g.blocks_x, g.blocks);
+    else
+        hipLaunchKernelGGL((stream_record_kernel<VoxelT, LAYOUT, BIG, false>), grid, block, 0, st, P, L.divmode_tc, view, (const VoxelT *)vol,
+                           (uint32_t)L.vol_bytes32, counts, block_elems, offsets, (VoxelT *)samples, g.blocks_x, g.blocks);
+    return hipGetLastError();
+}
+
+template <typename VoxelT>
+static hipError_t launch_record_type(const FrameParams &P, const LaunchConfig &L, const void *vol, uint16_t *counts, uint32_t *block_elems,
+                                     const uint64_t *offsets, void *samples, hipStream_t st)
+{
+    if (L.divmode_tc == DIV_EXACT) return hipErrorInvalidValue;      // (not a fast-path frame: the host never asks)
+    if (L.layout == 0)
+        return L.big_offsets ? launch_record_instance<VoxelT, 0, true>(P, L, vol, counts, block_elems, offsets, samples, st)
+                             : launch_record_instance<VoxelT, 0, false>(P, L, vol, counts, block_elems, offsets, samples, st);
+    return L.big_offsets ? launch_record_instance<VoxelT, 1, true>(P, L, vol, counts, block_elems, offsets, samples, st)
+                         : launch_record_instance<VoxelT, 1, false>(P, L, vol, counts, block_elems, offsets, samples, st);
+}
+
+// ------------------------------------------------------------------ replay
+// Workgroup = 512 threads = 8 wavefronts = one 32x16-pixel tile of the fast kernel's longest-first tile table; wavefront w of
+// tile (tx, ty) replays stream block (tx * 4 + (w & 3), ty * 2 + (w >> 2)).  No address tables, no barrier in the sample loop.
+// MODE: raymarch_fast_kernel's (vr_fast.hip:40-47).  LUT: classification through the LDS table -- the transfer function (MODE
+// >= 2) and its grey fold (MODE 0, FrameParams::tf_grey); the grey ramp is classified arithmetically (launch_replay_mode).
+// NOCLAMP: the dataset's exact range lies inside the window, so clamp() is the identity.
+typedef uint32_t stream_u32x2 __attribute__((ext_vector_type(2)));
+
+template <typename VoxelT, int MODE, bool LUT, bool NOCLAMP>
+__global__ __launch_bounds__(512) void raymarch_stream_kernel(const FrameParams P, const float4 *__restrict__ tf, float4 *__restrict__ fb,
+                                                              const VoxelT *__restrict__ samples, const uint16_t *__restrict__ counts,
+                                                              const uint64_t *__restrict__ offsets, const unsigned blocks_x,
+                                                              const uint32_t *__restrict__ tile_table)
+{
+    static_assert(LUT || MODE < 2, "a transfer function is classified through the LDS table");
+    static_assert(!NOCLAMP || (!LUT && MODE == 0), "the no-clamp specialisation exists for the grey composite's arithmetic classification");
+    __shared__ float lut[LUT ? FAST_LUT_MAX * 2 : 4];       // 32 KiB: 4096 x (c,a) or 256 x (r,g,b,a) + index bytes
+    const uint32_t t = tile_table[blockIdx.x];
+    if (t == 0xffffffffu) return;                            // padding block
+    const unsigned tx = t & 0xffffu, ty = t >> 16;
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const unsigned mx = lane & 7u, my = lane >> 3;
+    const int lx = (int)(tx * kFastTileW + (wave & 3u) * 8u + mx);
+    const int ly = (int)(ty * kFastTileH + (wave >> 2) * 8u + my);
+    const int px = lx;
+    int py;
+    if (P.stripe_count > 1) {
+        const int s = ly / P.stripe_rows, r = ly % P.stripe_rows;
+        py = (s * P.stripe_count + P.stripe_index) * P.stripe_rows + r;
+    } else {
+        py = P.row_begin + ly;
+    }
+    const bool in_image = !(px >= P.col_lim || py >= P.row_lim || py >= P.row_end);
+    const unsigned sb = (unsigned)__builtin_amdgcn_readfirstlane((int)((ty * 2u + (wave >> 2)) * blocks_x + tx * 4u + (wave & 3u)));
+    const int n = (int)counts[(size_t)sb * 64u + lane];      // 0: outside the image, or the ray misses the box
+    const uint64_t off = offsets[sb];
+    const uint32_t ngroups = (uint32_t)((offsets[sb + 1] - off) / STREAM_BLOCK_ELEMS);
+
+    if (LUT) {
+        // the classification table, exactly as raymarch_fast_kernel builds it (vr_fast.hip:100-144); tabulated only if some ray
+        // of the workgroup has a sample
+        if (__syncthreads_or(n > 0 ? 1 : 0)) {
+            const int ne = P.max_val - P.min_val + 1;
+            for (int e = (int)threadIdx.x; e < ne; e += 512) {
+                const float s = (float)(P.min_val + e);          // == clamp(float(texel), fmin, fmax)
+                const float v = div_cert(s - P.fmin, P.fden, P.rden);
+                if (MODE >= 2) {
+                    // classification through the transfer function: index = round(v*(len-1)), the entry from the table below
+                    int idx = floor_to_int_sat(v * (float)(P.tf_len - 1) + 0.5f);
+                    idx = clampi(idx, 0, P.tf_len - 1);
+                    reinterpret_cast<uint8_t *>(lut)[FAST_TF_ENTRIES * 16 + e] = (uint8_t)idx;
+                } else if (MODE == 0 && P.tf_grey != 0) {
+                    // a grey transfer function folded into the (c, a) table with MODE 2's own operations (vr_fast.hip:114-124)
+                    int idx = floor_to_int_sat(v * (float)(P.tf_len - 1) + 0.5f);
+                    idx = clampi(idx, 0, P.tf_len - 1);
+                    const float4 q = tf[idx];
+                    const float a = q.w * P.alpha_scale;
+                    lut[2 * e + 0] = q.x * a; lut[2 * e + 1] = a;
+                } else {
+                    const float a = v * P.alpha_scale;           // src.a *= alpha_scale, src.rgb *= src.a (VolumeRenderer.cs:130-131)
+                    lut[2 * e + 0] = v * a; lut[2 * e + 1] = a;
+                }
+            }
+            if (MODE >= 2) {
+                for (int e = (int)threadIdx.x; e < P.tf_len; e += 512) {
+                    const float4 q = tf[e];
+                    const float a = q.w * P.alpha_scale;
+                    if (MODE == 3) {            // MIP(): s *= alpha_scale on all four channels (VolumeRenderer.cs:164)
+                        lut[4 * e + 0] = q.x * P.alpha_scale; lut[4 * e + 1] = q.y * P.alpha_scale; lut[4 * e + 2] = q.z * P.alpha_scale;
+                    } else {                    // composite: src.a *= alpha_scale, src.rgb *= src.a (:130-131)
+                        lut[4 * e + 0] = q.x * a; lut[4 * e + 1] = q.y * a; lut[4 * e + 2] = q.z * a;
+                    }
+                    lut[4 * e + 3] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+
+    float drgb = 0.0f, dg = 0.0f, db = 0.0f, da = 0.0f;   // MODE 0/1: r == g == b bit for bit, only drgb is carried
+    if (ngroups != 0u) {
+        const int lut_bias = MODE >= 2 ? FAST_TF_ENTRIES * 16 - P.min_val : -8 * P.min_val;
+        uint32_t lut_entry0 = lds_offset_of(lut) + (uint32_t)lut_bias;
+        asm volatile("" : "+v"(lut_entry0));                 // a VECTOR register: no SGPR operand in the sample loop's VALU
+        // (the window's constants in VECTOR registers too: the table-less path has seven VALU operations per sample that read one)
+        float wfmin = P.fmin, wfmax = P.fmax, wfden = P.fden, wrden = P.rden, walpha = P.alpha_scale;
+        asm volatile("" : "+v"(wfmin), "+v"(wfmax), "+v"(wfden), "+v"(wrden), "+v"(walpha));
+        // window + classification of one texel -> premultiplied colour and opacity (classify of vr_fast.hip:192-216, on the raw
+        // voxel: the stream is no packed copy, there is no base to subtract)
+        auto classify = [&](uint32_t texel, float &c, float &cg, float &cb, float &a) {
+            if (LUT) {
+                int v = (int)texel;
+                if (!NOCLAMP) v = med3_i32(v, P.min_val, P.max_val);   // clamp(texel, min_val, max_val), min <= max
+                if (MODE >= 2) {
+                    const uint32_t idx = reinterpret_cast<const uint8_t *>(lut)[(uint32_t)(v + lut_bias)];
+                    const float4 q = reinterpret_cast<const float4 *>(lut)[idx];
+                    c = q.x; cg = q.y; cb = q.z; a = q.w;
+                } else {
+                    uint32_t entry;
+                    asm("v_lshl_add_u32 %0, %1, 3, %2" : "=v"(entry) : "v"(v), "v"(lut_entry0));
+                    VR_LDS_AS const float *ca = reinterpret_cast<VR_LDS_AS const float *>((size_t)entry);      // (one ds_read_b64)
+                    c = ca[0]; a = ca[1];
+                }
+            } else {
+                float s = (float)texel;
+                if (!NOCLAMP) s = fminf(fmaxf(s, wfmin), wfmax);   // operands are never NaN here
+                s = div_cert(s - wfmin, wfden, wrden);
+                a = s * walpha;
+                c = s * a;
+            }
+        };
+        // one sample onto the destination: front-to-back composite (VolumeRenderer.cs:132-133) or MIP's running maximum
+        // (:165-168) -- accumulate of vr_fast.hip:334-345
+        auto accumulate = [&](float c, float cg, float cb, float a) {
+            if (MODE == 1) {
+                if (da < a) da = a;
+            } else if (MODE == 3) {
+                if (da < a) { drgb = c; dg = cg; db = cb; da = a; }
+            } else {
+                const float om = 1.0f - da;
+                drgb += c * om;
+                if (MODE == 2) { dg += cg * om; db += cb * om; }
+                da += a * om;
+            }
+        };
+        using GroupT = typename std::conditional<sizeof(VoxelT) == 2, stream_u32x2, uint32_t>::type;
+        const GroupT *sp = reinterpret_cast<const GroupT *>(samples + off) + lane;
+        // group g of this lane; past the block's last group the last one is read again (its samples are never composited):
+        // the loop below is straight-line code with a fixed number of loads in flight
+        auto load_group = [&](uint32_t g) -> GroupT {
+            const GroupT *p = sp + (size_t)min(g, ngroups - 1u) * 64u;
+            return VR_STREAM_NT ? __builtin_nontemporal_load(p) : *p;
+        };
+        auto texel_of = [&](const GroupT &w, int u) -> uint32_t {
+            if constexpr (sizeof(VoxelT) == 2) return u & 1 ? w[u >> 1] >> 16 : w[u >> 1] & 0xffffu;
+            else return (w >> (8 * u)) & 0xffu;
+        };
+        bool alive = n > 0;
+        // the G samples i0 .. i0 + G - 1.  alpha_scale in [0,1] (fast-path precondition) makes dest.a non-decreasing and <= 1,
+        // so "dest.a < 0.95 before the LAST sample" proves the shader's per-sample test `dest.a >= 0.95 -> break`
+        // (VolumeRenderer.cs:118) passed for the whole group; the group in which a ray ends -- by that test or at its own n --
+        // runs the literal per-sample tests, and its padded slots are never composited
+        auto consume = [&](const GroupT &w, int i0) {
+            if (!alive) return;
+            float c[STREAM_G], cg[STREAM_G], cb[STREAM_G], a[STREAM_G];
+#pragma unroll
+            for (int u = 0; u < (int)STREAM_G; u++) { cg[u] = 0.0f; cb[u] = 0.0f; classify(texel_of(w, u), c[u], cg[u], cb[u], a[u]); }
+            const float drgb0 = drgb, dg0 = dg, db0 = db, da0 = da;
+            float da_last = 0.0f;
+#pragma unroll
+            for (int u = 0; u < (int)STREAM_G; u++) {
+                if (u == (int)STREAM_G - 1) da_last = da;
+                accumulate(c[u], cg[u], cb[u], a[u]);
+            }
+            if (i0 + (int)STREAM_G <= n && da_last < 0.95f) return;
+            drgb = drgb0; dg = dg0; db = db0; da = da0;
+#pragma unroll
+            for (int u = 0; u < (int)STREAM_G; u++) {
+                if (i0 + u >= n || da >= 0.95f) { alive = false; return; }
+                accumulate(c[u], cg[u], cb[u], a[u]);
+            }
+        };
+        constexpr int K = VR_STREAM_DEPTH;
+        GroupT cur[K], nxt[K];
+#pragma unroll
+        for (int k = 0; k < K; k++) cur[k] = load_group((uint32_t)k);
+        for (uint32_t g0 = 0; g0 < ngroups; g0 += (uint32_t)K) {
+#pragma unroll
+            for (int k = 0; k < K; k++) nxt[k] = load_group(g0 + (uint32_t)(K + k));
+#pragma unroll
+            for (int k = 0; k < K; k++) consume(cur[k], (int)((g0 + (uint32_t)k) * STREAM_G));
+#pragma unroll
+            for (int k = 0; k < K; k++) cur[k] = nxt[k];
+            if (__builtin_amdgcn_ballot_w64(alive) == 0ull) break;      // no lane of the wavefront is alive
+        }
+    }
+    if (!in_image) return;
+    const size_t pix = (size_t)(P.fb_compact ? ly : py) * (size_t)P.img_w + (size_t)px;
+    if (MODE >= 2) store_pixel(P, fb, pix, drgb, dg, db, da);
+    else if (MODE == 1) store_pixel(P, fb, pix, da, da, da, da);
+    else store_pixel(P, fb, pix, drgb, drgb, drgb, da);
+}
+
+template <typename VoxelT, int MODE>
+static hipError_t launch_replay_mode(const FrameParams &P, const LaunchConfig &L, const float4 *tf, float4 *fb, const RayStreamView &S, hipStream_t st)
+{
+    const StreamGrid g = streamGrid(P.img_w, launch_local_rows(P));
+    const dim3 grid(L.tile_table_blocks), block(512);
+    // The grey ramp is classified ARITHMETICALLY here, whatever the window: the table look-up (one ds_read_b64 per sample at a
+    // data-dependent address, what the gather kernels use) is what this kernel would wait for -- cfg3 0.246 ms with it, 0.226
+    // without (docs/lab-notebook.md) -- and the table's entries are these same operations, so the bits are the same.  Tables
+    // remain for the transfer function (MODE >= 2) and its grey fold.
+    const bool lut = MODE >= 2 ? L.use_lut != 0 : P.tf_grey != 0;
+#define VR_REPLAY(LT, NC)                                                                                                        \
+    hipLaunchKernelGGL((raymarch_stream_kernel<VoxelT, MODE, LT, NC>), grid, block, 0, st, P, tf, fb, (const VoxelT *)S.samples, \
+                       S.counts, S.offsets, g.blocks_x, L.tile_table)
+    if constexpr (MODE == 0) {
+        if (lut) VR_REPLAY(true, false);
+        else if (L.lut_noclamp != 0) VR_REPLAY(false, true);            // the data's exact range lies inside the window: clamp() is the identity
+        else VR_REPLAY(false, false);
+    } else if constexpr (MODE == 1) {
+        VR_REPLAY(false, false);
+    } else {
+        if (!lut) return hipErrorInvalidValue;               // (fast_path_eligible: a transfer function needs the table)
+        VR_REPLAY(true, false);
+    }
+#undef VR_REPLAY
+    return hipGetLastError();
+}
+
+// the mode as dispatch_fast2 picks it (vr_kernels.hip)
+template <typename VoxelT>
+static hipError_t launch_replay_type(const FrameParams &P, const LaunchConfig &L, const float4 *tf, float4 *fb, const RayStreamView &S, hipStream_t st)
+{
+    if (L.mip && P.tf_len > 1) return launch_replay_mode<VoxelT, 3>(P, L, tf, fb, S, st);
+    if (L.mip) return launch_replay_mode<VoxelT, 1>(P, L, tf, fb, S, st);
+    if (P.tf_len > 1 && P.tf_grey == 0) return launch_replay_mode<VoxelT, 2>(P, L, tf, fb, S, st);
+    return launch_replay_mode<VoxelT, 0>(P, L, tf, fb, S, st);
+}
+
+#if VR_STREAM_TU == 1 || VR_STREAM_TU == -1
+__global__ void warm_kernel_stream_u16() {}
+hipError_t launch_warm_stream_u16(hipStream_t st)
+{
+    hipLaunchKernelGGL(warm_kernel_stream_u16, dim3(1), dim3(64), 0, st);
+    return hipGetLastError();
+}
+hipError_t launch_stream_record_u16(const FrameParams &P, const LaunchConfig &L, const void *vol, uint16_t *counts, uint32_t *block_elems,
+                                    const uint64_t *offsets, void *samples, hipStream_t st)
+{
+    return launch_record_type<uint16_t>(P, L, vol, counts, block_elems, offsets, samples, st);
+}
+hipError_t launch_raymarch_stream_u16(const FrameParams &P, const LaunchConfig &L, const float4 *tf, float4 *fb, const RayStreamView &S, hipStream_t st)
+{
+    return launch_replay_type<uint16_t>(P, L, tf, fb, S, st);
+}
+#endif
+
+#if VR_STREAM_TU == 0 || VR_STREAM_TU == -1
+hipError_t launch_warm_stream_u16(hipStream_t st);
+hipError_t launch_stream_record_u16(const FrameParams &P, const LaunchConfig &L, const void *vol, uint16_t *counts, uint32_t *block_elems,
+                                    const uint64_t *offsets, void *samples, hipStream_t st);
+hipError_t launch_raymarch_stream_u16(const FrameParams &P, const LaunchConfig &L, const float4 *tf, float4 *fb, const RayStreamView &S, hipStream_t st);
+
+// exclusive scan of the blocks' padded lengths: one workgroup, every thread a contiguous run of blocks (a one-off of at most a
+// few hundred thousand entries)
+__global__ __launch_bounds__(1024) void stream_scan_kernel(const uint32_t *__restrict__ block_elems, uint64_t *__restrict__ offsets, const unsigned blocks)
+{
+    __shared__ uint64_t part[1024];
+    const unsigned per = (blocks + 1023u) / 1024u;
+    const unsigned b0 = min(threadIdx.x * per, blocks), b1 = min(b0 + per, blocks);
+    uint64_t sum = 0;
+    for (unsigned b = b0; b < b1; b++) sum += block_elems[b];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    for (unsigned d = 1; d < 1024u; d <<= 1) {               // inclusive Hillis-Steele scan of the 1024 partial sums
+        const uint64_t add = threadIdx.x >= d ? part[threadIdx.x - d] : 0ull;
+        __syncthreads();
+        part[threadIdx.x] += add;
+        __syncthreads();
+    }
+    uint64_t run = part[threadIdx.x] - sum;
+    for (unsigned b = b0; b < b1; b++) { offsets[b] = run; run += block_elems[b]; }
+    if (threadIdx.x == 1023u) offsets[blocks] = part[1023];
+}
+
+hipError_t launch_stream_scan(const uint32_t *block_elems, uint64_t *offsets, unsigned blocks, hipStream_t st)
+{
+    hipLaunchKernelGGL(stream_scan_kernel, dim3(1), dim3(1024), 0, st, block_elems, offsets, blocks);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_count(const FrameParams &P, const LaunchConfig &L, uint16_t *counts, uint32_t *block_elems, hipStream_t st)
+{
+    // (the count pass reads no voxel: the 8-bit instance serves both types)
+    return launch_record_type<uint8_t>(P, L, nullptr, counts, block_elems, nullptr, nullptr, st);
+}
+
+hipError_t launch_stream_record(const FrameParams &P, const LaunchConfig &L, const void *vol, const uint16_t *counts,
+                                const uint64_t *offsets, void *samples, hipStream_t st)
+{
+    if (samples == nullptr) return hipErrorInvalidValue;
+    uint16_t *c = const_cast<uint16_t *>(counts);            // (the record pass only reads them)
+    return L.bytes_per_voxel == 1 ? launch_record_type<uint8_t>(P, L, vol, c, nullptr, offsets, samples, st)
+                                  : launch_stream_record_u16(P, L, vol, c, nullptr, offsets, samples, st);
+}
+
+hipError_t launch_raymarch_stream(const FrameParams &P, const LaunchConfig &L, const float4 *tf, float4 *fb, const RayStreamView &S,
+                                  hipStream_t st, const char **kernel_name)
+{
+    if (launch_local_rows(P) <= 0 || P.img_w <= 0) return hipSuccess;
+    if (L.tile_table == nullptr || S.samples == nullptr) return hipErrorInvalidValue;
+    if (kernel_name) *kernel_name = "raymarch_stream_kernel";
+    return L.bytes_per_voxel == 1 ? launch_replay_type<uint8_t>(P, L, tf, fb, S, st) : launch_raymarch_stream_u16(P, L, tf, fb, S, st);
+}
+
+__global__ void warm_kernel_stream_u8() {}
+hipError_t launch_warm_stream(hipStream_t st)
+{
+    hipLaunchKernelGGL(warm_kernel_stream_u8, dim3(1), dim3(64), 0, st);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? launch_warm_stream_u16(st) : e;
+}
+#endif
+
+}  // namespace vr

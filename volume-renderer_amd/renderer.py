@@ -158,6 +158,9 @@ def load_library() -> C.CDLL:
         "vr_get_resident_bytes": (i32, [h, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "vr_set_copy_budget": (i32, [h, C.c_uint64]),
         "vr_get_copy_budget": (i32, [h, C.POINTER(C.c_uint64)]),
+        "vr_set_ray_stream": (i32, [h, i32]),
+        "vr_get_ray_stream_bytes": (i32, [h, C.POINTER(C.c_uint64)]),
+        "vr_get_ray_stream_builds": (i32, [h, C.POINTER(C.c_uint64)]),
         "vr_set_pack12": (i32, [h, i32]),
         "vr_get_pack12_bytes": (i32, [h, C.POINTER(C.c_size_t)]),
         "vr_set_trilinear_copy": (i32, [h, i32]),
@@ -849,6 +852,23 @@ class RendererCore:
     def copyBudget(self) -> int:
         b = C.c_uint64()
         self._check(self._lib.vr_get_copy_budget(self._h, C.byref(b)))
+        return b.value
+
+    RAY_STREAM_OFF, RAY_STREAM_AUTO, RAY_STREAM_BUILD = 0, 1, 2
+
+    def setRayStream(self, mode):
+        """the ray-ordered sample stream of a still view: 0 off, 1 automatic (default), 2 build at the next eligible frame"""
+        self._check(self._lib.vr_set_ray_stream(self._h, int(mode)))
+
+    def rayStreamBytes(self) -> int:
+        """device bytes of the valid stream (0 = none)"""
+        b = C.c_uint64()
+        self._check(self._lib.vr_get_ray_stream_bytes(self._h, C.byref(b)))
+        return b.value
+
+    def rayStreamBuilds(self) -> int:
+        b = C.c_uint64()
+        self._check(self._lib.vr_get_ray_stream_builds(self._h, C.byref(b)))
         return b.value
 
     def setTrilinearCopy(self, on):
