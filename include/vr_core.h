@@ -535,7 +535,9 @@ int vr_get_copy_budget(vr_handle h, uint64_t *bytes);
    rendered voxels makes the stream stale at once.  Building it runs two kernels and BLOCKS the calling thread once on an
    8-byte read-back (also inside vr_render_async).  The stream -- about 2 bytes (16-bit volumes) per sample of the frame plus
    padding, 1 GB for a 1024^3 volume at 1920x1080 -- is an optional copy: it counts under `copies` in vr_get_resident_bytes,
-   obeys vr_set_copy_budget (the first copy freed) and is dropped with the voxels.  vr_get_launch_choice is unaffected;
+   obeys vr_set_copy_budget (the first copy freed) and is dropped with the voxels.  Its size depends on the view, so a stream
+   that the budget or the device's memory refuses is refused for that geometry only -- not asked again while the geometry
+   stands, asked again after any change of it.  vr_get_launch_choice is unaffected;
    vr_get_last_kernel_name reports raymarch_stream_kernel on replayed frames.  Other mode values: VR_E_INVALID. */
 int vr_set_ray_stream(vr_handle h, int mode);
 /* device bytes of the valid stream (samples, per-pixel counts, block offsets); 0: none */

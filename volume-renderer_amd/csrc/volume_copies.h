@@ -31,9 +31,11 @@ public:
     void ensureSkipGrid(const ResidentVolume &V, size_t cells);
     // The ray-ordered sample stream of the launch (P, L): samples, per-pixel counts and block offsets.  true = valid for this
     // geometry (built now if it was not: count pass, scan, ONE blocking 8-byte read-back of the total, record pass).  false =
-    // refused like a copy.  invalidateRayStream: the geometry changed -- stale at once, the allocation is kept for the next build.
+    // refused for THIS geometry (budget / device memory; not asked again while it stands): unlike the copies' sizes the stream's
+    // depends on the view, so a refusal says nothing about the next one.  invalidateRayStream: the geometry changed -- stale at
+    // once, the allocation is kept for the next build, and a refusal is forgotten.
     bool ensureRayStream(const ResidentVolume &V, const FrameParams &P, const LaunchConfig &L);
-    void invalidateRayStream() { stream_valid_ = false; }
+    void invalidateRayStream() { stream_valid_ = false; stream_failed_ = false; }
     bool rayStreamValid() const { return stream_valid_; }
     RayStreamView rayStream() const { return {stream_samples_.get(), stream_counts_.get(), stream_offsets_.get()}; }
     uint64_t rayStreamBytes() const { return stream_valid_ ? rayStreamAllocated() : 0; }   // what a replayed frame holds resident
@@ -70,7 +72,7 @@ private:
     DeviceBuffer<uint8_t> stream_samples_;   // the ray-ordered sample stream (+ 16 bytes of slack)
     DeviceBuffer<uint16_t> stream_counts_;
     DeviceBuffer<uint64_t> stream_offsets_;
-    bool stream_valid_ = false, stream_failed_ = false;
+    bool stream_valid_ = false, stream_failed_ = false;   // failed: refused for this geometry, volume and budget
     uint64_t stream_elements_ = 0, stream_builds_ = 0;
 };
 
