@@ -544,6 +544,16 @@ int vr_set_ray_stream(vr_handle h, int mode);
 int vr_get_ray_stream_bytes(vr_handle h, uint64_t *bytes);
 /* how many streams this handle has built so far */
 int vr_get_ray_stream_builds(vr_handle h, uint64_t *builds);
+/* The stream's sample format.  A 16-bit volume whose exact range spans at most 4095 (12-bit CT data whatever its offset: the
+   rule of the 12-bit packed volume copy, vr_set_pack12) can keep its stream as voxel - minimum in 12 bits, eight samples per
+   12-byte load: a quarter fewer bytes resident, written by a build and read by every replayed frame, and the same frames bit
+   for bit.  mode 0: never; 1 (default): when the stream's samples would take more than 256 MiB unpacked (the last-level
+   cache of an MI355X: beyond it a replayed frame is an HBM stream); 2: whenever the volume allows.  8-bit volumes and wider
+   ranges keep the unpacked stream under every mode.  A new mode makes the stream stale: the next eligible launch builds it
+   again.  vr_get_last_kernel_name reports raymarch_stream12_kernel on frames replayed from a packed stream;
+   vr_get_ray_stream_bytes is the real allocation either way.  Other mode values: VR_E_INVALID. */
+int vr_set_ray_stream_pack(vr_handle h, int mode);
+int vr_get_ray_stream_pack(vr_handle h, int *mode);
 /* 1-D transfer function (N3): n knots of (iso in 0..255, r,g,b,a); n = 0 restores the
    reference grey ramp.  Built with the natural cubic spline of src/CubicSpline.cpp. */
 int vr_set_transfer_function(vr_handle h, const int32_t *iso, const float *rgba4, int n);

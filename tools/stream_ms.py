@@ -5,12 +5,15 @@ Shapes: cfg3 (bench.py's headline: 1024^3 u16 noise ball, 1920x1080, window [0,4
 sphere, 1280x720, alpha 1) and the cfg2 shape (512x512x452 u16, 1920x1080, window [1000,5095], alpha 0.05).  Per shape, after
 150 untimed frames (sustained clocks), tools/quick_ms.py's method -- the mean HIP-event kernel time of `--reps` blocking frames:
   gather_ms     vr_set_ray_stream 0: the measured choice's gather kernel (what the first frame of a new view costs)
-  replay_ms     vr_set_ray_stream 2: raymarch_stream_kernel
+  replay_ms     vr_set_ray_stream 2, vr_set_ray_stream_pack 0: raymarch_stream_kernel (the unpacked stream)
   build_ms      wall time of the frame that builds (count pass, scan, the blocking read-back, allocation, record pass) minus a
                 replayed frame's wall time; build_ms_again: a rebuild into the kept allocation (after a camera nudge)
   stream_bytes  vr_get_ray_stream_bytes; padding = the stream's sample bytes / (samples of the frame x bytes per voxel)
   floor_ms      stream_bytes / the vr_measure_stream_read rate of the same process
   bit_identical the replayed frame equals the gathered one, view(uint32)
+16-bit shapes also, under `packed` (vr_set_ray_stream_pack 2: raymarch_stream12_kernel, 12 bits per sample): replay_ms, build_ms (a
+build into the kept, larger allocation), stream_bytes (of a fresh handle's allocation: the model's packed size), floor_ms, x_floor,
+bit_identical, and automatic_packs -- whether the default mode packs this shape.
 cfg3 also: nudged_ms -- the camera nudged every frame in the default mode (the gather kernel, the key comparison on the host).
 
     python tools/stream_ms.py [--reps 40] [--out profiles/stream_ms.json] [--only cfg3]
@@ -57,6 +60,7 @@ def measure(vra, name, s, reps):
         r.generateSynthetic(R.SYNTH_SPHERE_U8 if s["synth"] == "sphere" else R.SYNTH_NOISE_BALL, s["dims"], s["bytes"], s["param"])
         r.setWindow(*s["window"]); r.setAlpha(s["alpha"])
         r.setRayStream(0)
+        r.setRayStreamPack(0)
         for _ in range(150):
             r.renderAsync()
         r.synchronize()
@@ -87,6 +91,23 @@ def measure(vra, name, s, reps):
         r.cameraOrient(0.0, 0.0005, 0.0)                               # a new view: the stream is rebuilt into the kept allocation
         out["build_ms_again"] = round(wall_ms(r) - replay_wall, 3)
         out["builds"] = r.rayStreamBuilds()
+        if s["bytes"] == 2:
+            r.setRayStream(0)                                          # (the nudged view: its own gathered frame to compare with)
+            r.render()
+            gathered = r.readPixels().copy()
+            r.setRayStream(2)
+            r.setRayStreamPack(2)
+            built = wall_ms(r)
+            replay_wall = min(wall_ms(r) for _ in range(5))
+            pk = {"build_ms": round(built - replay_wall, 3), "replay_ms": round(kernel_ms(r, reps), 4), "replay_kernel": r.last_kernel_name}
+            pk["bit_identical"] = bool(np.array_equal(r.readPixels().view(np.uint32), gathered.view(np.uint32)))
+            # the packed size from the unpacked one (the allocation on this handle is the kept, larger one): groups of 8 instead
+            # of 4 need the blocks' lengths, so it is read from a handle that only ever built the packed stream -- below
+            pk["stream_bytes_allocated_here"] = r.rayStreamBytes()
+            r.setRayStreamPack(1)
+            r.render()
+            pk["automatic_packs"] = r.last_kernel_name == pk["replay_kernel"]
+            out["packed"] = pk
         if name == "cfg3":
             r.setRayStream(1)
             runs = []
@@ -99,6 +120,20 @@ def measure(vra, name, s, reps):
             out["nudged_ms_runs"] = runs
             out["nudged_kernel"] = r.last_kernel_name
             out["builds_after_nudging"] = r.rayStreamBuilds()
+    if "packed" in out:
+        with vra.RendererCore(0) as r:                                 # a fresh handle: the packed stream's own allocation
+            r.setup(s["size"]); r.loadShader("VolumeRenderer.cs"); r.setQuirks(0)
+            r.generateSynthetic(R.SYNTH_NOISE_BALL, s["dims"], s["bytes"], s["param"])
+            r.setWindow(*s["window"]); r.setAlpha(s["alpha"])
+            r.setRayStreamPack(2); r.setRayStream(2)
+            built = wall_ms(r)
+            replay_wall = min(wall_ms(r) for _ in range(5))
+            pk = out["packed"]
+            pk["build_ms_fresh"] = round(built - replay_wall, 3)       # (includes the first allocation)
+            pk["stream_bytes"] = r.rayStreamBytes()
+            pk["floor_ms"] = round(pk["stream_bytes"] / (out["measured_stream_read_gbps"] * 1e9) * 1e3, 4)
+            pk["x_floor"] = round(pk["replay_ms"] / pk["floor_ms"], 2)
+            pk["speedup_over_unpacked"] = round(out["replay_ms"] / pk["replay_ms"], 3)
     return out
 
 

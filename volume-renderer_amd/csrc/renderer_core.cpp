@@ -769,6 +769,12 @@ void RendererCore::setRayStream(int mode)
     ray_stream_mode_ = mode;                                             // (0 keeps a valid stream: it is used again if the geometry still stands when the mode returns)
 }
 
+void RendererCore::setRayStreamPack(int mode)
+{
+    if (mode < 0 || mode > 2) throw std::invalid_argument("setRayStreamPack: unknown mode");
+    copies_.setRayStreamPack(mode);                                      // (another mode: the stream is stale, its allocation is kept)
+}
+
 // The ray-ordered sample stream (vr_stream.hip): counts this launch's geometry and decides whether the launch replays.  A launch
 // that cannot replay (another mode or filter, skipping, no tile table) or whose geometry differs from the last one's makes the
 // stream stale at once; its allocation is kept for the next build.  Mode 1: replay from the kRayStreamStillLaunches-th

@@ -129,6 +129,11 @@ public:
     uint64_t rayStreamBytes() const { return copies_.rayStreamBytes(); }
     uint64_t rayStreamElements() const { return copies_.rayStreamElements(); }
     uint64_t rayStreamBuilds() const { return copies_.rayStreamBuilds(); }
+    // The stream's format (vr_set_ray_stream_pack; vr_stream_pack.h): 0 never packs, 1 (default) packs a 16-bit volume whose exact
+    // range spans at most 4095 when the stream would be larger unpacked than the last-level cache, 2 packs whenever that range
+    // allows.  12 bits per sample instead of 16, the same frames bit for bit; a new mode rebuilds the stream.
+    void setRayStreamPack(int mode);
+    int rayStreamPack() const { return copies_.rayStreamPack(); }
     bool hasDevice() const { return device_ >= 0; }
     void warmTrilinear();                    // pre-load the staged TRILINEAR kernel's code objects (once)
     // first-hit isosurface mode (vr_set_isosurface): while on, frames are the shaded surface and its depth, whatever the MIP /
@@ -300,7 +305,7 @@ private:
     int present_count_ = 0;                  // frames enqueued so far
     void releasePresent();
     VolumeCopies copies_;                    // the packed copy, the apron copies and the skip grid: built lazily from d_vol_, dropped with its voxels
-    ResidentVolume residentVolume() const { return {d_vol_.get(), res_dims_[0], res_dims_[1], res_dims_[2], res_bytes_, vol_layout_, exact_min_, stream()}; }
+    ResidentVolume residentVolume() const { return {d_vol_.get(), res_dims_[0], res_dims_[1], res_dims_[2], res_bytes_, vol_layout_, exact_min_, exact_max_, stream()}; }
     size_t last_packed12_bytes_ = 0, last_apron_bytes_ = 0;   // packed copy / apron copies used by the last launch (0 = none)
     void refreshPacked12(FrameParams &P, LaunchConfig &L);
     void refreshApron(const FrameParams &P, LaunchConfig &L);

@@ -98,28 +98,46 @@ bool VolumeCopies::ensureRayStream(const ResidentVolume &V, const FrameParams &P
         if (!copyFits(n_counts * 2u + n_offsets * 8u) || !stream_counts_.tryAlloc(n_counts) || !stream_offsets_.tryAlloc(n_offsets)) return refuse();
     }
     uint64_t total = 0;
+    const int64_t span = (int64_t)V.exact_max - (int64_t)V.exact_min;
+    // mode 2 (and whatever can never pack) knows its format before the count; the automatic mode on a volume that could pack
+    // counts in groups of 4, learns the unpacked size and regroups to 8 if that size asks for the packed format
+    const bool undecided = stream_pack_mode_ == 1 && streamFormatFor(2, V.bytes_per_voxel, span, 0) == kStreamPack12;
+    StreamFormat format = undecided ? kStreamRaw : streamFormatFor(stream_pack_mode_, V.bytes_per_voxel, span, 0);
     {
         DeviceBuffer<uint32_t> block_elems;
         if (!block_elems.tryAlloc(g.blocks)) return refuse();
-        hipError_t e = launch_stream_count(P, L, stream_counts_.get(), block_elems.get(), V.stream);
-        if (e == hipSuccess) e = launch_stream_scan(block_elems.get(), stream_offsets_.get(), g.blocks, V.stream);
-        // the stream's length: the one blocking read-back of a build
-        if (e == hipSuccess) e = hipMemcpyAsync(&total, stream_offsets_.get() + g.blocks, sizeof(total), hipMemcpyDeviceToHost, V.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(V.stream);
+        auto scanTotal = [&]() {
+            hipError_t e = launch_stream_scan(block_elems.get(), stream_offsets_.get(), g.blocks, V.stream);
+            // the stream's length: the one blocking read-back of a build
+            if (e == hipSuccess) e = hipMemcpyAsync(&total, stream_offsets_.get() + g.blocks, sizeof(total), hipMemcpyDeviceToHost, V.stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(V.stream);
+            return e;
+        };
+        hipError_t e = launch_stream_count(P, L, stream_counts_.get(), block_elems.get(), streamGroupOf(format), V.stream);
+        if (e == hipSuccess) e = scanTotal();
+        if (e == hipSuccess && undecided) {
+            format = streamFormatFor(1, V.bytes_per_voxel, span, streamSampleBytes(kStreamRaw, V.bytes_per_voxel, total));
+            if (format == kStreamPack12) {
+                e = launch_stream_regroup(block_elems.get(), g.blocks, streamGroupOf(format), V.stream);
+                if (e == hipSuccess) e = scanTotal();
+            }
+        }
         if (e != hipSuccess) dropRayStream();
         hipCheck(e, "stream_record_kernel (count)");
     }
-    const uint64_t bytes = total * (uint64_t)V.bytes_per_voxel + 16u;
+    const uint64_t bytes = streamSampleBytes(format, V.bytes_per_voxel, total) + 16u;
     if (stream_samples_.bytes() < bytes) {
         stream_samples_.reset();                                         // (before the question whether the new one fits)
         if (!copyFits(bytes) || !stream_samples_.tryAlloc(bytes)) return refuse();
     }
     hipError_t e = hipSuccess;
-    if (total != 0) e = launch_stream_record(P, L, V.data, stream_counts_.get(), stream_offsets_.get(), stream_samples_.get(), V.stream);
+    if (total != 0) e = launch_stream_record(P, L, V.data, stream_counts_.get(), stream_offsets_.get(), stream_samples_.get(), format, V.exact_min, V.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(V.stream);
     if (e != hipSuccess) dropRayStream();
     hipCheck(e, "stream_record_kernel");
     stream_elements_ = total;
+    stream_format_ = format;
+    stream_base_ = format == kStreamPack12 ? V.exact_min : 0;
     stream_valid_ = true;
     stream_builds_++;
     return true;

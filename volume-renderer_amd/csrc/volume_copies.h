@@ -15,7 +15,7 @@ inline uint32_t bricksY(int n) { return (uint32_t)((n + BRICK_Y - 1) / BRICK_Y);
 inline uint32_t bricksZ(int n) { return (uint32_t)((n + BRICK_Z - 1) / BRICK_Z); }
 
 // the volume the copies are built from, and the stream the build kernels run on
-struct ResidentVolume { const void *data; int nx, ny, nz, bytes_per_voxel, layout, exact_min; hipStream_t stream; };
+struct ResidentVolume { const void *data; int nx, ny, nz, bytes_per_voxel, layout, exact_min, exact_max; hipStream_t stream; };
 
 class VolumeCopies {
 public:
@@ -34,10 +34,16 @@ public:
     // refused for THIS geometry (budget / device memory; not asked again while it stands): unlike the copies' sizes the stream's
     // depends on the view, so a refusal says nothing about the next one.  invalidateRayStream: the geometry changed -- stale at
     // once, the allocation is kept for the next build, and a refusal is forgotten.
+    // The format (vr_stream_pack.h: streamFormatFor) is chosen by the build from the pack mode, the volume and the size the
+    // stream has unpacked, and kept with the stream; a packed build in the automatic mode reads the total back a second time
+    // (the blocks are regrouped from 4 to 8 samples).  A new pack mode makes the stream stale like a new geometry.
     bool ensureRayStream(const ResidentVolume &V, const FrameParams &P, const LaunchConfig &L);
     void invalidateRayStream() { stream_valid_ = false; stream_failed_ = false; }
+    void setRayStreamPack(int mode) { if (mode != stream_pack_mode_) invalidateRayStream(); stream_pack_mode_ = mode; }
+    int rayStreamPack() const { return stream_pack_mode_; }
     bool rayStreamValid() const { return stream_valid_; }
-    RayStreamView rayStream() const { return {stream_samples_.get(), stream_counts_.get(), stream_offsets_.get()}; }
+    RayStreamView rayStream() const { return {stream_samples_.get(), stream_counts_.get(), stream_offsets_.get(), stream_format_, stream_base_}; }
+    StreamFormat rayStreamFormat() const { return stream_valid_ ? stream_format_ : kStreamRaw; }
     uint64_t rayStreamBytes() const { return stream_valid_ ? rayStreamAllocated() : 0; }   // what a replayed frame holds resident
     uint64_t rayStreamElements() const { return stream_valid_ ? stream_elements_ : 0; }    // samples incl. padding
     uint64_t rayStreamBuilds() const { return stream_builds_; }
@@ -74,6 +80,9 @@ private:
     DeviceBuffer<uint64_t> stream_offsets_;
     bool stream_valid_ = false, stream_failed_ = false;   // failed: refused for this geometry, volume and budget
     uint64_t stream_elements_ = 0, stream_builds_ = 0;
+    int stream_pack_mode_ = 1;               // vr_set_ray_stream_pack: 0 never, 1 automatic, 2 whenever lossless
+    StreamFormat stream_format_ = kStreamRaw;   // of the valid stream, with the base its packed samples are relative to
+    int stream_base_ = 0;
 };
 
 }  // namespace vr

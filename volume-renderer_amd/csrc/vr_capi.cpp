@@ -574,6 +574,19 @@ int vr_get_ray_stream_bytes(vr_handle h, uint64_t *bytes)
     });
 }
 
+int vr_set_ray_stream_pack(vr_handle h, int mode)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.setRayStreamPack(mode); });
+}
+
+int vr_get_ray_stream_pack(vr_handle h, int *mode)
+{
+    return guarded(h, [&](vr::RendererCore &c) {
+        if (!mode) throw std::invalid_argument("vr_get_ray_stream_pack: null result");
+        *mode = c.rayStreamPack();
+    });
+}
+
 int vr_get_ray_stream_builds(vr_handle h, uint64_t *builds)
 {
     return guarded(h, [&](vr::RendererCore &c) {

@@ -5,12 +5,13 @@
 
 #include "tile_schedule.h"
 #include "vr_frame.h"
+#include "vr_stream_pack.h"
 
 namespace vr {
 
 // The stream's blocks are the 8x8-pixel wavefront tiles of the fast kernel's 32x16-pixel workgroup tiles: 4 x 2 of them per
 // tile, whole tiles even where the image ends inside one (their lanes outside the image hold no sample).
-constexpr unsigned kStreamGroup = 4;          // G: samples a lane reads with one load
+constexpr unsigned kStreamGroup = 4;          // G: samples a lane reads with one load (the packed format: kStreamGroup12 = 8)
 struct StreamGrid { unsigned blocks_x, blocks_y, blocks; };
 inline StreamGrid streamGrid(int img_w, int rows)
 {
@@ -26,16 +27,23 @@ struct RayStreamView {
     const void *samples;          // VoxelT: sample i of lane l of block b at offsets[b] + (i / G) * 64 * G + l * G + i % G
     const uint16_t *counts;       // n per pixel, blocks * 64 (lane-major inside a block)
     const uint64_t *offsets;      // blocks + 1 element offsets; the last is the stream's length
+    // kStreamPack12 (16-bit volumes; vr_stream_pack.h): G = 8, a sample is voxel - base in 12 bits, group i / 8 of lane l is the
+    // three dwords at byte offsets[b] * 3 / 2 + (i / 8) * 768 + l * 12
+    StreamFormat format = kStreamRaw;
+    int base = 0;
 };
 
-// pass 1: the geometric sample count n of every ray into counts[blocks * 64] and n_max(block) * 64 -- n_max rounded up to G --
-// into block_elems[blocks]
-hipError_t launch_stream_count(const FrameParams &P, const LaunchConfig &L, uint16_t *counts, uint32_t *block_elems, hipStream_t st);
+// pass 1: the geometric sample count n of every ray into counts[blocks * 64] and n_max(block) * 64 -- n_max rounded up to
+// `group` -- into block_elems[blocks]
+hipError_t launch_stream_count(const FrameParams &P, const LaunchConfig &L, uint16_t *counts, uint32_t *block_elems, unsigned group, hipStream_t st);
+// block_elems of a smaller group size rounded up to whole groups of `group` (a multiple of it), in place
+hipError_t launch_stream_regroup(uint32_t *block_elems, unsigned blocks, unsigned group, hipStream_t st);
 // exclusive scan of block_elems into offsets[blocks + 1] (64-bit element offsets; offsets[blocks] = the total)
 hipError_t launch_stream_scan(const uint32_t *block_elems, uint64_t *offsets, unsigned blocks, hipStream_t st);
-// pass 2: the raw voxel of sample i of every ray into the stream (a padded slot holds voxel (0, 0, 0))
+// pass 2: the raw voxel of sample i of every ray into the stream (a padded slot holds voxel (0, 0, 0)); kStreamPack12:
+// voxel - base in 12 bits (a padded slot holds 0)
 hipError_t launch_stream_record(const FrameParams &P, const LaunchConfig &L, const void *vol, const uint16_t *counts,
-                                const uint64_t *offsets, void *samples, hipStream_t st);
+                                const uint64_t *offsets, void *samples, StreamFormat format, int base, hipStream_t st);
 // a frame from the stream: classification and compositing of every recorded sample (the fast kernel's modes; needs L.tile_table)
 hipError_t launch_raymarch_stream(const FrameParams &P, const LaunchConfig &L, const float4 *tf, float4 *fb, const RayStreamView &S,
                                   hipStream_t st, const char **kernel_name);

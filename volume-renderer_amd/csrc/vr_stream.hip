@@ -13,7 +13,8 @@
 // Layout: a block is one 8x8-pixel wavefront tile; n_max(block) = max n over its lanes rounded up to G; sample i of lane l sits
 // at offsets[block] + (i / G) * 64 * G + l * G + i % G: a wavefront instruction reads 512 (u16) / 256 (u8) contiguous bytes.
 //
-// Its own translation units (VR_STREAM_TU = 0: 8-bit volumes, the scan and the entry points; 1: 16-bit volumes), like
+// Its own translation units (VR_STREAM_TU = 0: 8-bit volumes, the scan and the entry points; 1: 16-bit volumes; 2: 16-bit
+// volumes in the 12-bit packed format, below and vr_stream_pack.h), like
 // vr_iso.hip: the vr_kernels.hip units are untouched, a frame whose camera moves runs the machine code it always ran.  Shared
 // with them is what vr_device.h offers; the classification table, classify and accumulate are restated from vr_fast.hip, each
 // with the shader lines it implements.  Arithmetic contract as in vr_kernels.hip (-ffp-contract=off, one rounding per step).
@@ -37,11 +38,20 @@
 #ifndef VR_STREAM_NT
 #define VR_STREAM_NT 1
 #endif
+// the same for the packed format, in groups of 8 samples (12 bytes): measured in docs/lab-notebook.md, "Ray stream: 12-bit samples"
+#ifndef VR_STREAM12_DEPTH
+#define VR_STREAM12_DEPTH 4
+#endif
 
 namespace vr {
 
 constexpr unsigned STREAM_G = kStreamGroup, STREAM_BLOCK_ELEMS = 64u * STREAM_G;
 static_assert(STREAM_G == 4, "a group is one 8-byte (u16) / 4-byte (u8) load: the packing below spells out four samples");
+// The packed format (vr_stream_pack.h; 16-bit volumes whose exact range spans at most 4095): G = 8 samples of 12 bits are one
+// 12-byte load, a wavefront instruction reads 768 contiguous bytes.  A block's element offset o is a multiple of 512, its byte
+// offset is o / 2 * 3.
+constexpr unsigned STREAM12_G = kStreamGroup12, STREAM12_BLOCK_ELEMS = 64u * STREAM12_G;
+static_assert(STREAM12_G == 2 * STREAM_G, "a packed group is consumed as two groups of four");
 
 // ------------------------------------------------------------------ build: count / record
 // One pixel per lane, 8x8 pixels per wavefront (= one stream block), four blocks per workgroup, over the launch's local rows:
@@ -50,13 +60,16 @@ static_assert(STREAM_G == 4, "a group is one 8-byte (u16) / 4-byte (u8) load: th
 // test and no compositing.  COUNT: n = iterations until a bound test fails (<= max_steps, fits 16 bits).  !COUNT: the same
 // positions once more, the bound tests replaced by i < n of the count pass, the fetches of 8 samples issued together (the
 // positions do not depend on the data); always from the resident volume, never from the packed copy.
-template <typename VoxelT, int LAYOUT, bool BIG, bool COUNT>
+// `group` (COUNT): the group size n_max is rounded up to.  PACK (!COUNT): the packed format -- voxel - base (P.pk12_base) in 12
+// bits, three dwords per lane per group of 8, 0 in a padded slot.
+template <typename VoxelT, int LAYOUT, bool BIG, bool COUNT, bool PACK = false>
 __global__ __launch_bounds__(256) void stream_record_kernel(const FrameParams P, const int divmode, const int view,
                                                             const VoxelT *__restrict__ vol, const uint32_t vol_bytes,
                                                             uint16_t *__restrict__ counts, uint32_t *__restrict__ block_elems,
                                                             const uint64_t *__restrict__ offsets, VoxelT *__restrict__ samples,
-                                                            const unsigned blocks_x, const unsigned blocks)
+                                                            const unsigned blocks_x, const unsigned blocks, const unsigned group)
 {
+    static_assert(!PACK || (!COUNT && sizeof(VoxelT) == 2), "the packed format holds 16-bit voxels");
     const unsigned lane = threadIdx.x & 63u;
     const unsigned sb = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
     if (sb >= blocks) return;
@@ -112,7 +125,40 @@ __global__ __launch_bounds__(256) void stream_record_kernel(const FrameParams P,
         int nmax = n;
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) nmax = max(nmax, __shfl_xor(nmax, d, 64));
-        if (lane == 0) block_elems[sb] = (((uint32_t)nmax + STREAM_G - 1u) / STREAM_G) * STREAM_BLOCK_ELEMS;
+        if (lane == 0) block_elems[sb] = (((uint32_t)nmax + group - 1u) / group) * (64u * group);
+    } else if constexpr (PACK) {
+        const int n = (int)counts[(size_t)sb * 64u + lane];
+        const uint64_t off = offsets[sb];
+        const uint32_t ngroups = (uint32_t)((offsets[sb + 1] - off) / STREAM12_BLOCK_ELEMS);
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)vol, 0, BIG ? 0 : (int)vol_bytes, 0x00020000);
+        // (the last group's last lane ends at byte (off + ngroups * 512) / 2 * 3: inside the allocation, before its slack)
+        uint32_t *out = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(samples) + off / 2u * 3u) + lane * 3u;
+        const uint32_t base = (uint32_t)P.pk12_base;
+        for (uint32_t g = 0; g < ngroups; g++) {
+            typename VoxelAddr<LAYOUT, BIG>::type a[8];
+            bool live[8];
+            uint32_t t[8], d[3];
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                live[u] = (int)(g * STREAM12_G) + u < n;
+                float tcx, tcy, tcz;
+                texcoord(x, y, z, tcx, tcy, tcz);
+                const int vi = max(min((int)(tcx * P.fdim[0]), P.nx - 1), 0);
+                const int vj = max(min((int)(tcy * P.fdim[1]), P.ny - 1), 0);
+                const int vk = max(min((int)(tcz * P.fdim[2]), P.nz - 1), 0);
+                a[u] = VoxelAddr<LAYOUT, BIG>::at(P, vi, vj, vk);
+                if (!live[u]) a[u] = 0;
+                x += dsx; y += dsy; z += dsz;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; u++) t[u] = VoxelFetch<VoxelT, BIG>::load(vol, rs, a[u]);
+            // (the mask only keeps a field inside its 12 bits should the host's range be wrong: base <= voxel <= base + 4095)
+#pragma unroll
+            for (int u = 0; u < 8; u++) t[u] = live[u] ? (t[u] - base) & 0xfffu : 0u;
+            stream_pack12(t, d);
+            uint32_t *q = out + (size_t)g * (64u * 3u);
+            q[0] = d[0]; q[1] = d[1]; q[2] = d[2];
+        }
     } else {
         const int n = (int)counts[(size_t)sb * 64u + lane];
         const uint64_t off = offsets[sb];
@@ -151,34 +197,38 @@ __global__ __launch_bounds__(256) void stream_record_kernel(const FrameParams P,
     }
 }
 
-template <typename VoxelT, int LAYOUT, bool BIG>
+template <typename VoxelT, int LAYOUT, bool BIG, bool PACK>
 static hipError_t launch_record_instance(const FrameParams &P, const LaunchConfig &L, const void *vol, uint16_t *counts,
-                                         uint32_t *block_elems, const uint64_t *offsets, void *samples, hipStream_t st)
+                                         uint32_t *block_elems, const uint64_t *offsets, void *samples, unsigned group, hipStream_t st)
 {
     const int rows = launch_local_rows(P);
     if (rows <= 0 || P.img_w <= 0) return hipSuccess;
     const StreamGrid g = streamGrid(P.img_w, rows);
     const int view = P.view_top == 1 ? 1 : (P.view_bottom == 1 ? 2 : 0);
     const dim3 grid((g.blocks + 3u) / 4u), block(256);
-    if (samples == nullptr)
+    if constexpr (PACK) {
+        if (samples == nullptr) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((stream_record_kernel<VoxelT, LAYOUT, BIG, false, true>), grid, block, 0, st, P, L.divmode_tc, view, (const VoxelT *)vol,
+                           (uint32_t)L.vol_bytes32, counts, block_elems, offsets, (VoxelT *)samples, g.blocks_x, g.blocks, group);
+    } else if (samples == nullptr)
         hipLaunchKernelGGL((stream_record_kernel<VoxelT, LAYOUT, BIG, true>), grid, block, 0, st, P, L.divmode_tc, view, (const VoxelT *)vol,
-                           (uint32_t)L.vol_bytes32, counts, block_elems, offsets, (VoxelT *)nullptr, g.blocks_x, g.blocks);
+                           (uint32_t)L.vol_bytes32, counts, block_elems, offsets, (VoxelT *)nullptr, g.blocks_x, g.blocks, group);
     else
         hipLaunchKernelGGL((stream_record_kernel<VoxelT, LAYOUT, BIG, false>), grid, block, 0, st, P, L.divmode_tc, view, (const VoxelT *)vol,
-                           (uint32_t)L.vol_bytes32, counts, block_elems, offsets, (VoxelT *)samples, g.blocks_x, g.blocks);
+                           (uint32_t)L.vol_bytes32, counts, block_elems, offsets, (VoxelT *)samples, g.blocks_x, g.blocks, group);
     return hipGetLastError();
 }
 
-template <typename VoxelT>
+template <typename VoxelT, bool PACK = false>
 static hipError_t launch_record_type(const FrameParams &P, const LaunchConfig &L, const void *vol, uint16_t *counts, uint32_t *block_elems,
-                                     const uint64_t *offsets, void *samples, hipStream_t st)
+                                     const uint64_t *offsets, void *samples, unsigned group, hipStream_t st)
 {
     if (L.divmode_tc == DIV_EXACT) return hipErrorInvalidValue;      // (not a fast-path frame: the host never asks)
     if (L.layout == 0)
-        return L.big_offsets ? launch_record_instance<VoxelT, 0, true>(P, L, vol, counts, block_elems, offsets, samples, st)
-                             : launch_record_instance<VoxelT, 0, false>(P, L, vol, counts, block_elems, offsets, samples, st);
-    return L.big_offsets ? launch_record_instance<VoxelT, 1, true>(P, L, vol, counts, block_elems, offsets, samples, st)
-                         : launch_record_instance<VoxelT, 1, false>(P, L, vol, counts, block_elems, offsets, samples, st);
+        return L.big_offsets ? launch_record_instance<VoxelT, 0, true, PACK>(P, L, vol, counts, block_elems, offsets, samples, group, st)
+                             : launch_record_instance<VoxelT, 0, false, PACK>(P, L, vol, counts, block_elems, offsets, samples, group, st);
+    return L.big_offsets ? launch_record_instance<VoxelT, 1, true, PACK>(P, L, vol, counts, block_elems, offsets, samples, group, st)
+                         : launch_record_instance<VoxelT, 1, false, PACK>(P, L, vol, counts, block_elems, offsets, samples, group, st);
 }
 
 // ------------------------------------------------------------------ replay
@@ -187,9 +237,16 @@ static hipError_t launch_record_type(const FrameParams &P, const LaunchConfig &L
 // MODE: raymarch_fast_kernel's (vr_fast.hip:40-47).  LUT: classification through the LDS table -- the transfer function (MODE
 // >= 2) and its grey fold (MODE 0, FrameParams::tf_grey); the grey ramp is classified arithmetically (launch_replay_mode).
 // NOCLAMP: the dataset's exact range lies inside the window, so clamp() is the identity.
+//
+// PACK ("raymarch_stream12_kernel"): the packed format.  A sample is t = voxel - base (P.pk12_base, the stream's own) and the
+// base is folded into constants, so the sample loop has the unpacked format's operations after the unpack:
+//  - table paths: clamp(voxel, min, max) + bias == clamp(t, min - base, max - base) + (bias + base), integers throughout;
+//  - arithmetic path: the window is shifted, fmin - base and fmax - base (vr_stream_pack.h: streamBaseFoldsIntoWindow has the
+//    reasoning and the bound); BASEADD, for a window beyond that bound: t + base as an integer before the convert.
 typedef uint32_t stream_u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t stream_u32x3 __attribute__((ext_vector_type(3)));   // (a register value only: never loaded through a pointer of this type)
 
-template <typename VoxelT, int MODE, bool LUT, bool NOCLAMP>
+template <typename VoxelT, int MODE, bool LUT, bool NOCLAMP, bool PACK = false, bool BASEADD = false>
 __global__ __launch_bounds__(512) void raymarch_stream_kernel(const FrameParams P, const float4 *__restrict__ tf, float4 *__restrict__ fb,
                                                               const VoxelT *__restrict__ samples, const uint16_t *__restrict__ counts,
                                                               const uint64_t *__restrict__ offsets, const unsigned blocks_x,
@@ -197,6 +254,9 @@ __global__ __launch_bounds__(512) void raymarch_stream_kernel(const FrameParams 
 {
     static_assert(LUT || MODE < 2, "a transfer function is classified through the LDS table");
     static_assert(!NOCLAMP || (!LUT && MODE == 0), "the no-clamp specialisation exists for the grey composite's arithmetic classification");
+    static_assert(!PACK || sizeof(VoxelT) == 2, "the packed format holds 16-bit voxels");
+    static_assert(!BASEADD || (PACK && !LUT), "the integer add replaces the shifted window of the arithmetic path");
+    constexpr unsigned G = PACK ? STREAM12_G : STREAM_G, BLOCK_ELEMS = 64u * G;
     __shared__ float lut[LUT ? FAST_LUT_MAX * 2 : 4];       // 32 KiB: 4096 x (c,a) or 256 x (r,g,b,a) + index bytes
     const uint32_t t = tile_table[blockIdx.x];
     if (t == 0xffffffffu) return;                            // padding block
@@ -217,7 +277,7 @@ __global__ __launch_bounds__(512) void raymarch_stream_kernel(const FrameParams 
     const unsigned sb = (unsigned)__builtin_amdgcn_readfirstlane((int)((ty * 2u + (wave >> 2)) * blocks_x + tx * 4u + (wave & 3u)));
     const int n = (int)counts[(size_t)sb * 64u + lane];      // 0: outside the image, or the ray misses the box
     const uint64_t off = offsets[sb];
-    const uint32_t ngroups = (uint32_t)((offsets[sb + 1] - off) / STREAM_BLOCK_ELEMS);
+    const uint32_t ngroups = (uint32_t)((offsets[sb + 1] - off) / BLOCK_ELEMS);
 
     if (LUT) {
         // the classification table, exactly as raymarch_fast_kernel builds it (vr_fast.hip:100-144); tabulated only if some ray
@@ -262,18 +322,22 @@ __global__ __launch_bounds__(512) void raymarch_stream_kernel(const FrameParams 
 
     float drgb = 0.0f, dg = 0.0f, db = 0.0f, da = 0.0f;   // MODE 0/1: r == g == b bit for bit, only drgb is carried
     if (ngroups != 0u) {
-        const int lut_bias = MODE >= 2 ? FAST_TF_ENTRIES * 16 - P.min_val : -8 * P.min_val;
+        // (the packed format's base: 0 otherwise)
+        const int base = PACK ? P.pk12_base : 0;
+        const int cmin = P.min_val - base, cmax = P.max_val - base;
+        const int lut_bias = MODE >= 2 ? FAST_TF_ENTRIES * 16 - cmin : -8 * cmin;
         uint32_t lut_entry0 = lds_offset_of(lut) + (uint32_t)lut_bias;
         asm volatile("" : "+v"(lut_entry0));                 // a VECTOR register: no SGPR operand in the sample loop's VALU
         // (the window's constants in VECTOR registers too: the table-less path has seven VALU operations per sample that read one)
         float wfmin = P.fmin, wfmax = P.fmax, wfden = P.fden, wrden = P.rden, walpha = P.alpha_scale;
+        if (PACK && !BASEADD) { wfmin -= (float)base; wfmax -= (float)base; }      // exact (streamBaseFoldsIntoWindow)
         asm volatile("" : "+v"(wfmin), "+v"(wfmax), "+v"(wfden), "+v"(wrden), "+v"(walpha));
         // window + classification of one texel -> premultiplied colour and opacity (classify of vr_fast.hip:192-216, on the raw
-        // voxel: the stream is no packed copy, there is no base to subtract)
+        // voxel: the stream is no packed copy, there is no base to subtract; PACK: on voxel - base, against the shifted constants)
         auto classify = [&](uint32_t texel, float &c, float &cg, float &cb, float &a) {
             if (LUT) {
                 int v = (int)texel;
-                if (!NOCLAMP) v = med3_i32(v, P.min_val, P.max_val);   // clamp(texel, min_val, max_val), min <= max
+                if (!NOCLAMP) v = med3_i32(v, cmin, cmax);             // clamp(texel, min_val, max_val), min <= max
                 if (MODE >= 2) {
                     const uint32_t idx = reinterpret_cast<const uint8_t *>(lut)[(uint32_t)(v + lut_bias)];
                     const float4 q = reinterpret_cast<const float4 *>(lut)[idx];
@@ -306,28 +370,42 @@ __global__ __launch_bounds__(512) void raymarch_stream_kernel(const FrameParams 
                 da += a * om;
             }
         };
-        using GroupT = typename std::conditional<sizeof(VoxelT) == 2, stream_u32x2, uint32_t>::type;
-        const GroupT *sp = reinterpret_cast<const GroupT *>(samples + off) + lane;
+        using GroupT = typename std::conditional<PACK, stream_u32x3, typename std::conditional<sizeof(VoxelT) == 2, stream_u32x2, uint32_t>::type>::type;
+        // (PACK: the block's bytes begin at off / 2 * 3, a lane's 12 bytes of a group at l * 12 of the group's 768)
+        using SlotT = typename std::conditional<PACK, uint32_t, GroupT>::type;
+        constexpr unsigned SLOTS = PACK ? 3u : 1u;           // of SlotT per lane per group
+        const SlotT *sp = PACK ? reinterpret_cast<const SlotT *>(reinterpret_cast<const uint8_t *>(samples) + off / 2u * 3u) + lane * SLOTS
+                               : reinterpret_cast<const SlotT *>(samples + off) + lane;
         // group g of this lane; past the block's last group the last one is read again (its samples are never composited):
         // the loop below is straight-line code with a fixed number of loads in flight
         auto load_group = [&](uint32_t g) -> GroupT {
-            const GroupT *p = sp + (size_t)min(g, ngroups - 1u) * 64u;
-            return VR_STREAM_NT ? __builtin_nontemporal_load(p) : *p;
+            const SlotT *p = sp + (size_t)min(g, ngroups - 1u) * (64u * SLOTS);
+            if constexpr (PACK) {                            // (three dword loads at one address: the compiler makes them one of 12 bytes)
+                GroupT w;
+                w.x = VR_STREAM_NT ? __builtin_nontemporal_load(p) : p[0];
+                w.y = VR_STREAM_NT ? __builtin_nontemporal_load(p + 1) : p[1];
+                w.z = VR_STREAM_NT ? __builtin_nontemporal_load(p + 2) : p[2];
+                return w;
+            } else {
+                return VR_STREAM_NT ? __builtin_nontemporal_load(p) : *p;
+            }
         };
         auto texel_of = [&](const GroupT &w, int u) -> uint32_t {
-            if constexpr (sizeof(VoxelT) == 2) return u & 1 ? w[u >> 1] >> 16 : w[u >> 1] & 0xffffu;
+            if constexpr (PACK) return stream_unpack12(w.x, w.y, w.z, u) + (BASEADD ? (uint32_t)base : 0u);
+            else if constexpr (sizeof(VoxelT) == 2) return u & 1 ? w[u >> 1] >> 16 : w[u >> 1] & 0xffffu;
             else return (w >> (8 * u)) & 0xffu;
         };
         bool alive = n > 0;
         // the G samples i0 .. i0 + G - 1.  alpha_scale in [0,1] (fast-path precondition) makes dest.a non-decreasing and <= 1,
         // so "dest.a < 0.95 before the LAST sample" proves the shader's per-sample test `dest.a >= 0.95 -> break`
         // (VolumeRenderer.cs:118) passed for the whole group; the group in which a ray ends -- by that test or at its own n --
-        // runs the literal per-sample tests, and its padded slots are never composited
-        auto consume = [&](const GroupT &w, int i0) {
+        // runs the literal per-sample tests, and its padded slots are never composited.  u0: the first of the four inside the
+        // load's group (PACK: a group of 8 is consumed as two groups of four, u0 = 0 and 4)
+        auto consume = [&](const GroupT &w, int i0, int u0) {
             if (!alive) return;
             float c[STREAM_G], cg[STREAM_G], cb[STREAM_G], a[STREAM_G];
 #pragma unroll
-            for (int u = 0; u < (int)STREAM_G; u++) { cg[u] = 0.0f; cb[u] = 0.0f; classify(texel_of(w, u), c[u], cg[u], cb[u], a[u]); }
+            for (int u = 0; u < (int)STREAM_G; u++) { cg[u] = 0.0f; cb[u] = 0.0f; classify(texel_of(w, u0 + u), c[u], cg[u], cb[u], a[u]); }
             const float drgb0 = drgb, dg0 = dg, db0 = db, da0 = da;
             float da_last = 0.0f;
 #pragma unroll
@@ -343,7 +421,7 @@ __global__ __launch_bounds__(512) void raymarch_stream_kernel(const FrameParams 
                 accumulate(c[u], cg[u], cb[u], a[u]);
             }
         };
-        constexpr int K = VR_STREAM_DEPTH;
+        constexpr int K = PACK ? VR_STREAM12_DEPTH : VR_STREAM_DEPTH;
         GroupT cur[K], nxt[K];
 #pragma unroll
         for (int k = 0; k < K; k++) cur[k] = load_group((uint32_t)k);
@@ -351,7 +429,10 @@ __global__ __launch_bounds__(512) void raymarch_stream_kernel(const FrameParams 
 #pragma unroll
             for (int k = 0; k < K; k++) nxt[k] = load_group(g0 + (uint32_t)(K + k));
 #pragma unroll
-            for (int k = 0; k < K; k++) consume(cur[k], (int)((g0 + (uint32_t)k) * STREAM_G));
+            for (int k = 0; k < K; k++) {
+                consume(cur[k], (int)((g0 + (uint32_t)k) * G), 0);
+                if (PACK) consume(cur[k], (int)((g0 + (uint32_t)k) * G + STREAM_G), (int)STREAM_G);
+            }
 #pragma unroll
             for (int k = 0; k < K; k++) cur[k] = nxt[k];
             if (__builtin_amdgcn_ballot_w64(alive) == 0ull) break;      // no lane of the wavefront is alive
@@ -364,7 +445,7 @@ __global__ __launch_bounds__(512) void raymarch_stream_kernel(const FrameParams 
     else store_pixel(P, fb, pix, drgb, drgb, drgb, da);
 }
 
-template <typename VoxelT, int MODE>
+template <typename VoxelT, int MODE, bool PACK>
 static hipError_t launch_replay_mode(const FrameParams &P, const LaunchConfig &L, const float4 *tf, float4 *fb, const RayStreamView &S, hipStream_t st)
 {
     const StreamGrid g = streamGrid(P.img_w, launch_local_rows(P));
@@ -374,6 +455,28 @@ static hipError_t launch_replay_mode(const FrameParams &P, const LaunchConfig &L
     // without (docs/lab-notebook.md) -- and the table's entries are these same operations, so the bits are the same.  Tables
     // remain for the transfer function (MODE >= 2) and its grey fold.
     const bool lut = MODE >= 2 ? L.use_lut != 0 : P.tf_grey != 0;
+    if constexpr (PACK) {
+        // the stream's own base travels in the frame's parameters (pk12_base is otherwise the packed volume copy's, which the
+        // replay never reads); a window the shifted constants cannot hold exactly takes the integer add (BASEADD)
+        FrameParams Q = P;
+        Q.pk12_base = S.base;
+        const bool shift = streamBaseFoldsIntoWindow(P.min_val, P.max_val, S.base);
+#define VR_REPLAY12(LT, NC, BA)                                                                                                   \
+    hipLaunchKernelGGL((raymarch_stream_kernel<VoxelT, MODE, LT, NC, true, BA>), grid, block, 0, st, Q, tf, fb,                  \
+                       (const VoxelT *)S.samples, S.counts, S.offsets, g.blocks_x, L.tile_table)
+        if constexpr (MODE == 0) {
+            if (lut) VR_REPLAY12(true, false, false);
+            else if (L.lut_noclamp != 0) { if (shift) VR_REPLAY12(false, true, false); else VR_REPLAY12(false, true, true); }
+            else { if (shift) VR_REPLAY12(false, false, false); else VR_REPLAY12(false, false, true); }
+        } else if constexpr (MODE == 1) {
+            if (shift) VR_REPLAY12(false, false, false); else VR_REPLAY12(false, false, true);
+        } else {
+            if (!lut) return hipErrorInvalidValue;
+            VR_REPLAY12(true, false, false);
+        }
+#undef VR_REPLAY12
+        return hipGetLastError();
+    } else {
 #define VR_REPLAY(LT, NC)                                                                                                        \
     hipLaunchKernelGGL((raymarch_stream_kernel<VoxelT, MODE, LT, NC>), grid, block, 0, st, P, tf, fb, (const VoxelT *)S.samples, \
                        S.counts, S.offsets, g.blocks_x, L.tile_table)
@@ -389,17 +492,39 @@ static hipError_t launch_replay_mode(const FrameParams &P, const LaunchConfig &L
     }
 #undef VR_REPLAY
     return hipGetLastError();
+    }
 }
 
 // the mode as dispatch_fast2 picks it (vr_kernels.hip)
-template <typename VoxelT>
+template <typename VoxelT, bool PACK = false>
 static hipError_t launch_replay_type(const FrameParams &P, const LaunchConfig &L, const float4 *tf, float4 *fb, const RayStreamView &S, hipStream_t st)
 {
-    if (L.mip && P.tf_len > 1) return launch_replay_mode<VoxelT, 3>(P, L, tf, fb, S, st);
-    if (L.mip) return launch_replay_mode<VoxelT, 1>(P, L, tf, fb, S, st);
-    if (P.tf_len > 1 && P.tf_grey == 0) return launch_replay_mode<VoxelT, 2>(P, L, tf, fb, S, st);
-    return launch_replay_mode<VoxelT, 0>(P, L, tf, fb, S, st);
+    if (L.mip && P.tf_len > 1) return launch_replay_mode<VoxelT, 3, PACK>(P, L, tf, fb, S, st);
+    if (L.mip) return launch_replay_mode<VoxelT, 1, PACK>(P, L, tf, fb, S, st);
+    if (P.tf_len > 1 && P.tf_grey == 0) return launch_replay_mode<VoxelT, 2, PACK>(P, L, tf, fb, S, st);
+    return launch_replay_mode<VoxelT, 0, PACK>(P, L, tf, fb, S, st);
 }
+
+#if VR_STREAM_TU == 2 || VR_STREAM_TU == -1
+// the packed format's instances (16-bit volumes)
+__global__ void warm_kernel_stream_p12() {}
+hipError_t launch_warm_stream_p12(hipStream_t st)
+{
+    hipLaunchKernelGGL(warm_kernel_stream_p12, dim3(1), dim3(64), 0, st);
+    return hipGetLastError();
+}
+hipError_t launch_stream_record_p12(const FrameParams &P, const LaunchConfig &L, const void *vol, uint16_t *counts, const uint64_t *offsets,
+                                    void *samples, int base, hipStream_t st)
+{
+    FrameParams Q = P;
+    Q.pk12_base = base;
+    return launch_record_type<uint16_t, true>(Q, L, vol, counts, nullptr, offsets, samples, STREAM12_G, st);
+}
+hipError_t launch_raymarch_stream_p12(const FrameParams &P, const LaunchConfig &L, const float4 *tf, float4 *fb, const RayStreamView &S, hipStream_t st)
+{
+    return launch_replay_type<uint16_t, true>(P, L, tf, fb, S, st);
+}
+#endif
 
 #if VR_STREAM_TU == 1 || VR_STREAM_TU == -1
 __global__ void warm_kernel_stream_u16() {}
@@ -411,7 +536,7 @@ hipError_t launch_warm_stream_u16(hipStream_t st)
 hipError_t launch_stream_record_u16(const FrameParams &P, const LaunchConfig &L, const void *vol, uint16_t *counts, uint32_t *block_elems,
                                     const uint64_t *offsets, void *samples, hipStream_t st)
 {
-    return launch_record_type<uint16_t>(P, L, vol, counts, block_elems, offsets, samples, st);
+    return launch_record_type<uint16_t>(P, L, vol, counts, block_elems, offsets, samples, STREAM_G, st);
 }
 hipError_t launch_raymarch_stream_u16(const FrameParams &P, const LaunchConfig &L, const float4 *tf, float4 *fb, const RayStreamView &S, hipStream_t st)
 {
@@ -424,6 +549,10 @@ hipError_t launch_warm_stream_u16(hipStream_t st);
 hipError_t launch_stream_record_u16(const FrameParams &P, const LaunchConfig &L, const void *vol, uint16_t *counts, uint32_t *block_elems,
                                     const uint64_t *offsets, void *samples, hipStream_t st);
 hipError_t launch_raymarch_stream_u16(const FrameParams &P, const LaunchConfig &L, const float4 *tf, float4 *fb, const RayStreamView &S, hipStream_t st);
+hipError_t launch_warm_stream_p12(hipStream_t st);
+hipError_t launch_stream_record_p12(const FrameParams &P, const LaunchConfig &L, const void *vol, uint16_t *counts, const uint64_t *offsets,
+                                    void *samples, int base, hipStream_t st);
+hipError_t launch_raymarch_stream_p12(const FrameParams &P, const LaunchConfig &L, const float4 *tf, float4 *fb, const RayStreamView &S, hipStream_t st);
 
 // exclusive scan of the blocks' padded lengths: one workgroup, every thread a contiguous run of blocks (a one-off of at most a
 // few hundred thousand entries)
@@ -453,18 +582,37 @@ hipError_t launch_stream_scan(const uint32_t *block_elems, uint64_t *offsets, un
     return hipGetLastError();
 }
 
-hipError_t launch_stream_count(const FrameParams &P, const LaunchConfig &L, uint16_t *counts, uint32_t *block_elems, hipStream_t st)
+// block lengths counted for a smaller group size, rounded up to whole groups of `group` (a multiple of it): ceil_8(ceil_4(n)) ==
+// ceil_8(n), so the count pass need not run again when the format is chosen from the unpacked size
+__global__ __launch_bounds__(256) void stream_regroup_kernel(uint32_t *__restrict__ block_elems, const unsigned blocks, const unsigned group)
 {
+    const unsigned b = blockIdx.x * 256u + threadIdx.x;
+    if (b >= blocks) return;
+    block_elems[b] = ((block_elems[b] / 64u + group - 1u) / group) * (64u * group);
+}
+
+hipError_t launch_stream_regroup(uint32_t *block_elems, unsigned blocks, unsigned group, hipStream_t st)
+{
+    if (blocks == 0u || group == 0u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stream_regroup_kernel, dim3((blocks + 255u) / 256u), dim3(256), 0, st, block_elems, blocks, group);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_count(const FrameParams &P, const LaunchConfig &L, uint16_t *counts, uint32_t *block_elems, unsigned group, hipStream_t st)
+{
+    if (group == 0u) return hipErrorInvalidValue;
     // (the count pass reads no voxel: the 8-bit instance serves both types)
-    return launch_record_type<uint8_t>(P, L, nullptr, counts, block_elems, nullptr, nullptr, st);
+    return launch_record_type<uint8_t>(P, L, nullptr, counts, block_elems, nullptr, nullptr, group, st);
 }
 
 hipError_t launch_stream_record(const FrameParams &P, const LaunchConfig &L, const void *vol, const uint16_t *counts,
-                                const uint64_t *offsets, void *samples, hipStream_t st)
+                                const uint64_t *offsets, void *samples, StreamFormat format, int base, hipStream_t st)
 {
     if (samples == nullptr) return hipErrorInvalidValue;
     uint16_t *c = const_cast<uint16_t *>(counts);            // (the record pass only reads them)
-    return L.bytes_per_voxel == 1 ? launch_record_type<uint8_t>(P, L, vol, c, nullptr, offsets, samples, st)
+    if (format == kStreamPack12)
+        return L.bytes_per_voxel == 2 ? launch_stream_record_p12(P, L, vol, c, offsets, samples, base, st) : hipErrorInvalidValue;
+    return L.bytes_per_voxel == 1 ? launch_record_type<uint8_t>(P, L, vol, c, nullptr, offsets, samples, STREAM_G, st)
                                   : launch_stream_record_u16(P, L, vol, c, nullptr, offsets, samples, st);
 }
 
@@ -473,6 +621,11 @@ hipError_t launch_raymarch_stream(const FrameParams &P, const LaunchConfig &L, c
 {
     if (launch_local_rows(P) <= 0 || P.img_w <= 0) return hipSuccess;
     if (L.tile_table == nullptr || S.samples == nullptr) return hipErrorInvalidValue;
+    if (S.format == kStreamPack12) {
+        if (L.bytes_per_voxel != 2) return hipErrorInvalidValue;
+        if (kernel_name) *kernel_name = "raymarch_stream12_kernel";
+        return launch_raymarch_stream_p12(P, L, tf, fb, S, st);
+    }
     if (kernel_name) *kernel_name = "raymarch_stream_kernel";
     return L.bytes_per_voxel == 1 ? launch_replay_type<uint8_t>(P, L, tf, fb, S, st) : launch_raymarch_stream_u16(P, L, tf, fb, S, st);
 }
@@ -481,8 +634,9 @@ __global__ void warm_kernel_stream_u8() {}
 hipError_t launch_warm_stream(hipStream_t st)
 {
     hipLaunchKernelGGL(warm_kernel_stream_u8, dim3(1), dim3(64), 0, st);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? launch_warm_stream_u16(st) : e;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = launch_warm_stream_u16(st);
+    return e == hipSuccess ? launch_warm_stream_p12(st) : e;
 }
 #endif
 

@@ -161,6 +161,8 @@ def load_library() -> C.CDLL:
         "vr_set_ray_stream": (i32, [h, i32]),
         "vr_get_ray_stream_bytes": (i32, [h, C.POINTER(C.c_uint64)]),
         "vr_get_ray_stream_builds": (i32, [h, C.POINTER(C.c_uint64)]),
+        "vr_set_ray_stream_pack": (i32, [h, i32]),
+        "vr_get_ray_stream_pack": (i32, [h, C.POINTER(i32)]),
         "vr_set_pack12": (i32, [h, i32]),
         "vr_get_pack12_bytes": (i32, [h, C.POINTER(C.c_size_t)]),
         "vr_set_trilinear_copy": (i32, [h, i32]),
@@ -870,6 +872,18 @@ class RendererCore:
         b = C.c_uint64()
         self._check(self._lib.vr_get_ray_stream_builds(self._h, C.byref(b)))
         return b.value
+
+    RAY_STREAM_PACK_OFF, RAY_STREAM_PACK_AUTO, RAY_STREAM_PACK_ALWAYS = 0, 1, 2
+
+    def setRayStreamPack(self, mode):
+        """the stream's 12-bit packed format (16-bit volumes spanning at most 4095): 0 never, 1 automatic (default: streams
+        larger than the last-level cache), 2 whenever the volume allows"""
+        self._check(self._lib.vr_set_ray_stream_pack(self._h, int(mode)))
+
+    def rayStreamPack(self) -> int:
+        m = C.c_int32()
+        self._check(self._lib.vr_get_ray_stream_pack(self._h, C.byref(m)))
+        return m.value
 
     def setTrilinearCopy(self, on):
         self._check(self._lib.vr_set_trilinear_copy(self._h, int(bool(on))))
