@@ -2,7 +2,8 @@
 over both voxel types, both layouts, shapes that are no multiple of a brick or a tile and axes shorter than the radius; that
 smoothing never accumulates and (0, 0, 0) restores the loaded volume and every mode's frame; that everything built from the
 voxels (packed copy, apron copies, skip grid, ranges, tile order) follows them, by comparing with a fresh handle that was
-given the CPU-smoothed voxels; what the call keeps; layout changes; and a volume beyond 32-bit byte offsets on sampled voxels."""
+given the CPU-smoothed voxels; what the call keeps; layout changes; and a volume beyond 32-bit byte offsets on sampled voxels.
+The kernels at the limits of their LDS ring, column segments, x tiles and z slabs: tests/test_smoothing_edges_gpu.py."""
 import importlib.util
 from pathlib import Path
 
