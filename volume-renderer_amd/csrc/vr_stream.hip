@@ -7,6 +7,9 @@
 // copy that holds the same voxels (like the 12-bit packed copy): frames are bit-identical, and every replayed frame still
 // classifies and composites every sample, so window, alpha, transfer-function and MIP changes render from the same stream.
 //
+// The replay loop (raymarch_stream_kernel): a wavefront replays one block and keeps DEPTH loaded groups beyond the DEPTH it
+// composites; the instances without a classification table run as one-wavefront workgroups, eight per tile.
+//
 // Build (once per still view; VolumeCopies::ensureRayStream): stream_record_kernel<COUNT> writes the geometric sample count n
 // of every ray, a device scan turns the blocks' padded lengths into 64-bit element offsets, the host reads the total back --
 // ONE blocking 8-byte read-back per build -- allocates, and stream_record_kernel<!COUNT> writes the voxels.
@@ -42,6 +45,13 @@
 #ifndef VR_STREAM12_DEPTH
 #define VR_STREAM12_DEPTH 4
 #endif
+// threads per workgroup of the table-less instances: 64, 128, 256, or 512 (one tile per workgroup, like the instances with a
+// table): measured in docs/lab-notebook.md, "Ray stream: wave-uniform replay"
+#ifndef VR_STREAM_WG
+#define VR_STREAM_WG 64
+#endif
+static_assert(VR_STREAM_WG == 64 || VR_STREAM_WG == 128 || VR_STREAM_WG == 256 || VR_STREAM_WG == 512,
+              "a tile's eight wavefronts are split into 8, 4, 2 or 1 workgroups");
 
 namespace vr {
 
@@ -234,6 +244,9 @@ static hipError_t launch_record_type(const FrameParams &P, const LaunchConfig &L
 // ------------------------------------------------------------------ replay
 // Workgroup = 512 threads = 8 wavefronts = one 32x16-pixel tile of the fast kernel's longest-first tile table; wavefront w of
 // tile (tx, ty) replays stream block (tx * 4 + (w & 3), ty * 2 + (w >> 2)).  No address tables, no barrier in the sample loop.
+// An instance without a table (LUT false) uses no LDS and no barrier at all: its tiles are launched as 512 / VR_STREAM_WG
+// workgroups of VR_STREAM_WG threads each, in the table's order -- a wavefront's slot is free for the next tile's as soon as
+// that wavefront ends, not when the slowest of its eight does.
 // MODE: raymarch_fast_kernel's (vr_fast.hip:40-47).  LUT: classification through the LDS table -- the transfer function (MODE
 // >= 2) and its grey fold (MODE 0, FrameParams::tf_grey); the grey ramp is classified arithmetically (launch_replay_mode).
 // NOCLAMP: the dataset's exact range lies inside the window, so clamp() is the identity.
@@ -258,10 +271,12 @@ __global__ __launch_bounds__(512) void raymarch_stream_kernel(const FrameParams 
     static_assert(!BASEADD || (PACK && !LUT), "the integer add replaces the shifted window of the arithmetic path");
     constexpr unsigned G = PACK ? STREAM12_G : STREAM_G, BLOCK_ELEMS = 64u * G;
     __shared__ float lut[LUT ? FAST_LUT_MAX * 2 : 4];       // 32 KiB: 4096 x (c,a) or 256 x (r,g,b,a) + index bytes
-    const uint32_t t = tile_table[blockIdx.x];
+    // (a table-less instance uses no LDS and no barrier: its tile may be launched as 8 / WPB workgroups of WPB wavefronts)
+    constexpr unsigned WPB = LUT ? 8u : (unsigned)VR_STREAM_WG / 64u, SPLIT = 8u / WPB;
+    const uint32_t t = tile_table[blockIdx.x / SPLIT];
     if (t == 0xffffffffu) return;                            // padding block
     const unsigned tx = t & 0xffffu, ty = t >> 16;
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const unsigned lane = threadIdx.x & 63u, wave = (blockIdx.x % SPLIT) * WPB + (threadIdx.x >> 6);
     const unsigned mx = lane & 7u, my = lane >> 3;
     const int lx = (int)(tx * kFastTileW + (wave & 3u) * 8u + mx);
     const int ly = (int)(ty * kFastTileH + (wave >> 2) * 8u + my);
@@ -450,6 +465,10 @@ static hipError_t launch_replay_mode(const FrameParams &P, const LaunchConfig &L
 {
     const StreamGrid g = streamGrid(P.img_w, launch_local_rows(P));
     const dim3 grid(L.tile_table_blocks), block(512);
+    // (a table-less instance's grid: 512 / VR_STREAM_WG workgroups per tile, their product kept inside a grid's 2^31 - 1)
+    constexpr unsigned SPLIT = 512u / (unsigned)VR_STREAM_WG;
+    if (L.tile_table_blocks > 0x7fffffffu / SPLIT) return hipErrorInvalidValue;
+    const dim3 grid_nolut(L.tile_table_blocks * SPLIT), block_nolut((unsigned)VR_STREAM_WG);
     // The grey ramp is classified ARITHMETICALLY here, whatever the window: the table look-up (one ds_read_b64 per sample at a
     // data-dependent address, what the gather kernels use) is what this kernel would wait for -- cfg3 0.246 ms with it, 0.226
     // without (docs/lab-notebook.md) -- and the table's entries are these same operations, so the bits are the same.  Tables
@@ -462,7 +481,7 @@ static hipError_t launch_replay_mode(const FrameParams &P, const LaunchConfig &L
         Q.pk12_base = S.base;
         const bool shift = streamBaseFoldsIntoWindow(P.min_val, P.max_val, S.base);
 #define VR_REPLAY12(LT, NC, BA)                                                                                                   \
-    hipLaunchKernelGGL((raymarch_stream_kernel<VoxelT, MODE, LT, NC, true, BA>), grid, block, 0, st, Q, tf, fb,                  \
+    hipLaunchKernelGGL((raymarch_stream_kernel<VoxelT, MODE, LT, NC, true, BA>), LT ? grid : grid_nolut, LT ? block : block_nolut, 0, st, Q, tf, fb, \
                        (const VoxelT *)S.samples, S.counts, S.offsets, g.blocks_x, L.tile_table)
         if constexpr (MODE == 0) {
             if (lut) VR_REPLAY12(true, false, false);
@@ -478,7 +497,7 @@ static hipError_t launch_replay_mode(const FrameParams &P, const LaunchConfig &L
         return hipGetLastError();
     } else {
 #define VR_REPLAY(LT, NC)                                                                                                        \
-    hipLaunchKernelGGL((raymarch_stream_kernel<VoxelT, MODE, LT, NC>), grid, block, 0, st, P, tf, fb, (const VoxelT *)S.samples, \
+    hipLaunchKernelGGL((raymarch_stream_kernel<VoxelT, MODE, LT, NC>), LT ? grid : grid_nolut, LT ? block : block_nolut, 0, st, P, tf, fb, (const VoxelT *)S.samples, \
                        S.counts, S.offsets, g.blocks_x, L.tile_table)
     if constexpr (MODE == 0) {
         if (lut) VR_REPLAY(true, false);
