@@ -2,8 +2,8 @@
 voxel of the buffer, cameras inside / grazing / far, images smaller than a tile, zero gradients, max == min, the +1000 quirk, the
 truncated grid, the 10 000-step budget, the tail of the reslice loop and iso values that meet a stored value exactly.
 
-vr_iso.hip, vr_reslice.hip and vr_shade.hip share one sampler (csrc/vr_sampler.h) but each wraps its own march, gradient and
-reduction around it; the composite kernels' edge tests (the tiny volumes of test_parity_gpu.py) do not reach them.  Every
+vr_iso.hip, vr_reslice.hip and vr_shade.hip share one sampler (csrc/vr_sampler.h), iso and shade also the ray start and the skip
+cell (csrc/vr_march.h), but each wraps its own march loop, gradient and reduction around them; the composite kernels' edge tests (the tiny volumes of test_parity_gpu.py) do not reach them.  Every
 comparison is against the mode's CPU definition (tests/iso_ref, tests/reslice_ref, tests/shade_ref; tests/test_mode_edges_cpu.py
 anchors those at the same edges) on every output the mode has -- RGBA bits, per-pixel counts, depth bits, reslice value bits.
 Windows and iso values are in STORED units and the handles run with setQuirks(0), unless a case says that it converts through

@@ -16,6 +16,7 @@
 #include "launch_plan.h"
 #include "tile_schedule.h"
 #include "volume_io.h"
+#include "vr_code_unit.h"
 #include "vr_iso.h"
 #include "vr_reslice.h"
 #include "vr_shade.h"
@@ -150,15 +151,7 @@ bool RendererCore::loadShader(std::string fn, bool reload)
     // instead of by the first render() (a cold first launch costs ~16 ms)
     if (device_ >= 0) {
         requireDevice("loadShader");
-        check(launch_warm_modules(stream()), "module pre-load");
-        check(launch_warm_iso(stream()), "module pre-load (isosurface)");
-        check(launch_warm_reslice(stream()), "module pre-load (reslice)");
-        check(launch_warm_shade(stream()), "module pre-load (shading)");
-        check(launch_warm_smooth(stream()), "module pre-load (smoothing)");
-        check(launch_warm_mesh(stream()), "module pre-load (extraction)");
-        check(launch_warm_components(stream()), "module pre-load (components)");
-        check(launch_warm_simplify(stream()), "module pre-load (simplification)");
-        check(launch_warm_stream(stream()), "module pre-load (sample stream)");
+        warmUnits(WARM_LOAD_SHADER);
         check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
         tslab_warm_ = false;
         if (filter == 1) warmTrilinear();
@@ -810,11 +803,18 @@ void RendererCore::engageRayStream(PreparedLaunch &F, const uint32_t *spp)
 // the LDS-staged TRILINEAR kernel's seven code objects (vr_tslab.hip), loaded when TRILINEAR is selected -- vr_set_filter,
 // or vr_load_shader with the filter already set -- not by the first frame that needs one of them (round-4 advisor: the
 // measured choice tries several shapes mid-interaction, each of which would pay a lazy decompress + load)
+void RendererCore::warmUnits(int group)
+{
+    const char *family = nullptr;
+    const hipError_t e = launch_warm_units((WarmGroup)group, stream(), &family);
+    check(e, family ? std::string("module pre-load (") + family + ")" : std::string("module pre-load: a kernel unit without its VR_CODE_UNIT line"));
+}
+
 void RendererCore::warmTrilinear()
 {
     if (device_ < 0 || tslab_warm_ || !cs_program_) return;
     requireDevice("warmTrilinear");
-    check(launch_warm_tslab(stream()), "module pre-load (trilinear)");
+    warmUnits(WARM_TRILINEAR);
     check(hipStreamSynchronize(stream()), "hipStreamSynchronize");
     tslab_warm_ = true;
 }

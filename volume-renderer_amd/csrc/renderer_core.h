@@ -349,7 +349,8 @@ private:
 
     hipStream_t stream() const { return user_stream_ ? user_stream_ : own_stream_; }
     void requireDevice(const char *what) const;
-    void check(hipError_t e, const char *what) const { hipCheck(e, what); }
+    void check(hipError_t e, const std::string &what) const { hipCheck(e, what); }
+    void warmUnits(int group);               // one empty launch per code object of a WarmGroup (vr_code_unit.h)
     void freeVolume();
     void dropDerived();                      // everything built from the voxels of d_vol_: packed copy, apron copies, skip grid, the tile order under skipping
     void allocVolume(int nx, int ny, int nz, int bytes, int layout);

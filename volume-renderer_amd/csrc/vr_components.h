@@ -48,7 +48,4 @@ hipError_t launch_components_records(const ComponentsJob &J, hipStream_t st);   
 // bit v of `plane` (component_words words) = voxel v's component is selected (selected: one byte per component)
 hipError_t launch_components_plane(const uint32_t *labels, const uint8_t *selected, uint64_t n_voxels, uint64_t *plane, hipStream_t st);
 
-// one empty launch per translation unit: loads their code objects (vr_load_shader)
-hipError_t launch_warm_components(hipStream_t st);
-
 }  // namespace vr

@@ -25,11 +25,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vr_code_unit.h"
 #include "vr_components.h"
 #include "vr_frame.h"
 
 #ifndef VR_COMP_TU
-#define VR_COMP_TU -1
+#error "VR_COMP_TU: the unit number comes from the build"
 #endif
 
 namespace vr {
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(kTileThreads) void comp_tile_kernel(const CompArgs 
     }
 }
 
-#if VR_COMP_TU == 0 || VR_COMP_TU == -1
+#if VR_COMP_TU == 0
 // ------------------------------------------------------------------ union-find in memory (the seam pass, flatten)
 constexpr uint32_t kFindCap = 1u << 20, kUnionCap = 1u << 12;
 // the +x face, the rest of the +y face, the rest of the +z face
@@ -429,31 +430,14 @@ hipError_t launch_tiles_type(const ComponentsJob &J, hipStream_t st)
 
 }  // namespace
 
-#if VR_COMP_TU == 0 || VR_COMP_TU == -1
-hipError_t launch_components_tiles_u8(const ComponentsJob &J, hipStream_t st) { return launch_tiles_type<uint8_t>(J, st); }
-#endif
-#if VR_COMP_TU == 1 || VR_COMP_TU == -1
+VR_CODE_UNIT(components, VR_COMP_TU, "components", WARM_LOAD_SHADER)
+
+#if VR_COMP_TU == 1
 hipError_t launch_components_tiles_u16(const ComponentsJob &J, hipStream_t st) { return launch_tiles_type<uint16_t>(J, st); }
-#endif
-
-// one empty kernel per unit: launching it makes the runtime inflate and load that unit's code object
-#if VR_COMP_TU >= 0
-#define VR_COMP_CAT2(a, b) a##b
-#define VR_COMP_CAT(a, b) VR_COMP_CAT2(a, b)
-__global__ void VR_COMP_CAT(warm_kernel_components, VR_COMP_TU)() {}
-hipError_t VR_COMP_CAT(launch_warm_components_tu, VR_COMP_TU)(hipStream_t st)
-{
-    hipLaunchKernelGGL(VR_COMP_CAT(warm_kernel_components, VR_COMP_TU), dim3(1), dim3(64), 0, st);
-    return hipGetLastError();
-}
-#endif
-
+#else
 // the unit of 8-bit volumes also carries the entry points and the kernels that never read a voxel
-#if VR_COMP_TU == 0 || VR_COMP_TU == -1
-#if VR_COMP_TU == 0
+hipError_t launch_components_tiles_u8(const ComponentsJob &J, hipStream_t st) { return launch_tiles_type<uint8_t>(J, st); }
 hipError_t launch_components_tiles_u16(const ComponentsJob &J, hipStream_t st);
-hipError_t launch_warm_components_tu1(hipStream_t st);
-#endif
 
 namespace {
 
@@ -522,18 +506,6 @@ hipError_t launch_components_plane(const uint32_t *labels, const uint8_t *select
     const uint64_t words = (n_voxels + 63) / 64;
     hipLaunchKernelGGL(comp_plane_kernel, grid_of((words * 64 + 255) / 256), dim3(256), 0, st, labels, selected, n_voxels, words, plane);
     return hipGetLastError();
-}
-
-hipError_t launch_warm_components(hipStream_t st)
-{
-#if VR_COMP_TU == 0
-    hipError_t e = launch_warm_components_tu0(st);
-    if (e == hipSuccess) e = launch_warm_components_tu1(st);
-    return e;
-#else
-    (void)st;
-    return hipSuccess;
-#endif
 }
 #endif
 

@@ -42,21 +42,8 @@ __global__ __launch_bounds__(256) void raymarch_generic_kernel(const FrameParams
                 const float fi = (float)i;
                 qx = p0x + fi * dsx; qy = p0y + fi * dsy; qz = p0z + fi * dsz;
             }
-            // cartesianToTextureCoord (VolumeRenderer.cs:175-192)
-            float ux = qx + P.half[0], uy = qy + P.half[1], uz = qz + P.half[2];
-            if (divmode == DIV_CERT) {
-                ux = div_cert(ux, P.ext[0], P.rext[0]);
-                uy = div_cert(uy, P.ext[1], P.rext[1]);
-                uz = div_cert(uz, P.ext[2], P.rext[2]);
-            } else {
-                ux = ux / P.ext[0]; uy = uy / P.ext[1]; uz = uz / P.ext[2];
-            }
-            const float uzr = uz;   // z before the flip of :185
-            uz = 1.0f - uz;
             float tcx, tcy, tcz;
-            if (P.view_top == 1) { tcx = ux; tcy = uzr; tcz = uy; }   // 1 - (1 - z) as the GL compiles it: z
-            else if (P.view_bottom == 1) { tcx = ux; tcy = uz; tcz = 1.0f - uy; }
-            else { tcx = ux; tcy = uy; tcz = uz; }
+            texcoord(P, divmode, qx, qy, qz, tcx, tcy, tcz);
             if (tcx > 1.0f || tcy > 1.0f || tcz > 1.0f || tcx < 0.0f || tcy < 0.0f || tcz < 0.0f || d3 >= 0.95f)
                 break;
             float s;

@@ -19,7 +19,4 @@ struct IsoArgs {
 hipError_t launch_raymarch_iso(const FrameParams &P, const LaunchConfig &L, const IsoArgs &A, const void *vol, const float4 *tf,
                                float4 *fb, uint32_t *spp, hipStream_t st, const char **kernel_name);
 
-// one empty launch per iso translation unit: loads their code objects (vr_load_shader)
-hipError_t launch_warm_iso(hipStream_t st);
-
 }  // namespace vr

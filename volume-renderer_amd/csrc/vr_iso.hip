@@ -3,7 +3,8 @@
 // two-sided headlight.  The definition, step by step, is in include/vr_core.h and DESIGN.md section 1; tests/iso_ref/iso_ref.c
 // restates it on the CPU and tests/test_isosurface_gpu.py holds this kernel to it bit for bit.
 //
-// Its own translation units (VR_ISO_TU = 0: 8-bit volumes, 1: 16-bit volumes), like vr_tslab.hip: the vr_kernels.hip units,
+// Its own translation units (VR_ISO_TU = 0: 8-bit volumes and the entry point, 1: 16-bit volumes; the build always sets it, and
+// VR_CODE_UNIT registers each for the pre-load), like vr_tslab.hip; launched through mode_dispatch.h: the vr_kernels.hip units,
 // FrameParams and LaunchConfig are untouched by the mode, the iso value, the depth target and the skip grid are extra
 // kernel arguments.  Arithmetic contract as in vr_kernels.hip: one correctly rounded fp32 operation per step, nothing
 // contracted (-ffp-contract=off), the only fused operations are explicit: TRILINEAR's lerps (tri_lerp) and the certified
@@ -14,14 +15,17 @@
 // (TRILINEAR: of the lower tap), so a sample in a cell whose DILATED maximum (the cell and its 26 neighbours) is below the iso
 // value is below it too and is not fetched.  The grid is read when the ray enters a new cell, not per step; positions still
 // advance sample by sample with the shader's additions, so hits, counts and frames are the same bits with and without it.
+// The ray start and the skip cell are vr_march.h's, shared with vr_shade.hip; gradient, normal and headlight are written out here.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "vr_sampler.h"
+#include "mode_dispatch.h"
+#include "vr_code_unit.h"
+#include "vr_march.h"
 #include "vr_iso.h"
 
 #ifndef VR_ISO_TU
-#define VR_ISO_TU -1
+#error "VR_ISO_TU: the unit number comes from the build"
 #endif
 
 namespace vr {
@@ -45,24 +49,20 @@ __global__ __launch_bounds__(256) void raymarch_iso_kernel(const FrameParams P, 
     uint32_t samples = 0;
     if (intersect_ray_aabb(P, ray, t_min, t_max)) {
         const VolumeSampler<VoxelT, LAYOUT, BIG> S(P, vol, vol_bytes);
-        auto nearest_index = [&](float tc, float fdim, int n) -> int { return clampi(floor_to_int_sat(tc * fdim), 0, n - 1); };
         auto sample_at = [&](float tcx, float tcy, float tcz) -> float {
             if (FILTER == 0)
                 return S.voxel(nearest_index(tcx, P.fdim[0], P.nx), nearest_index(tcy, P.fdim[1], P.ny), nearest_index(tcz, P.fdim[2], P.nz));
             return S.trilinear(tcx * P.fdim[0] - 0.5f, tcy * P.fdim[1] - 0.5f, tcz * P.fdim[2] - 0.5f);
         };
 
-        const float EPSILON = 0.000001f;
-        const float sx = ray.ox + ray.dx * t_min, sy = ray.oy + ray.dy * t_min, sz = ray.oz + ray.dz * t_min;
-        const float p0x = sx + ray.dx * EPSILON, p0y = sy + ray.dy * EPSILON, p0z = sz + ray.dz * EPSILON;
-        const float dsx = ray.dx * P.step, dsy = ray.dy * P.step, dsz = ray.dz * P.step;
+        const RayStart R = ray_start(P, ray, t_min);
+        const float p0x = R.p0x, p0y = R.p0y, p0z = R.p0z, dsx = R.dsx, dsy = R.dsy, dsz = R.dsz;
         float qx = p0x, qy = p0y, qz = p0z;          // q_i
         float rx = p0x, ry = p0y, rz = p0z;          // q_{i-1}
         float s_prev = 0.0f, s_hit = 0.0f;
         bool prev_fetched = false, hit = false;
         int i = 0;
-        uint32_t cell = 0xffffffffu;
-        bool cell_empty = false;
+        SkipCell skip;
         // ---- the march: the composite mode's positions and box-exit test (without its dest.a term), no window, no compositing
         for (; i < P.max_steps; i++) {
             if (P.accum == 1) {
@@ -79,16 +79,11 @@ __global__ __launch_bounds__(256) void raymarch_iso_kernel(const FrameParams P, 
                 if (FILTER == 0) {
                     ci = nearest_index(tcx, P.fdim[0], P.nx); cj = nearest_index(tcy, P.fdim[1], P.ny); ck = nearest_index(tcz, P.fdim[2], P.nz);
                 } else {
-                    ci = clampi((int)floorf(tcx * P.fdim[0] - 0.5f), 0, P.nx - 1);
-                    cj = clampi((int)floorf(tcy * P.fdim[1] - 0.5f), 0, P.ny - 1);
-                    ck = clampi((int)floorf(tcz * P.fdim[2] - 0.5f), 0, P.nz - 1);
+                    ci = lower_tap(tcx * P.fdim[0] - 0.5f, P.nx);
+                    cj = lower_tap(tcy * P.fdim[1] - 0.5f, P.ny);
+                    ck = lower_tap(tcz * P.fdim[2] - 0.5f, P.nz);
                 }
-                const uint32_t c = ((uint32_t)ci >> 3) + (uint32_t)P.cnx * (((uint32_t)cj >> 3) + (uint32_t)P.cny * ((uint32_t)ck >> 3));
-                if (c != cell) {
-                    cell = c;
-                    cell_empty = (float)grid[c] < iso_s;
-                }
-                fetch = !cell_empty;
+                fetch = !skip.enter(P, grid, ci, cj, ck, [&](uint16_t cell_max) { return (float)cell_max < iso_s; });
             }
             if (fetch) {
                 const float s = sample_at(tcx, tcy, tcz);
@@ -169,83 +164,35 @@ __global__ __launch_bounds__(256) void raymarch_iso_kernel(const FrameParams P, 
     if (spp) spp[pix] = samples;
 }
 
-template <typename VoxelT, int LAYOUT, int FILTER, bool SKIP>
-static hipError_t launch_iso(const FrameParams &P, const LaunchConfig &L, const IsoArgs &A, const void *vol, const float4 *tf, float4 *fb,
-                             uint32_t *spp, unsigned tiles_x, unsigned tiles_y, hipStream_t st)
-{
-    const int div = L.divmode_tc == DIV_EXACT ? DIV_EXACT : DIV_CERT;
-    const dim3 grid(padded_blocks(tiles_x, tiles_y)), block(256);
-    if (L.big_offsets)
-        hipLaunchKernelGGL((raymarch_iso_kernel<VoxelT, LAYOUT, FILTER, SKIP, true>), grid, block, 0, st, P, div, 0u, (const VoxelT *)vol, tf,
-                           fb, spp, A.depth, A.skip_grid, A.iso_s, tiles_x, tiles_y);
-    else
-        hipLaunchKernelGGL((raymarch_iso_kernel<VoxelT, LAYOUT, FILTER, SKIP, false>), grid, block, 0, st, P, div, (uint32_t)L.vol_bytes32,
-                           (const VoxelT *)vol, tf, fb, spp, A.depth, A.skip_grid, A.iso_s, tiles_x, tiles_y);
-    return hipGetLastError();
-}
-
 template <typename VoxelT>
 static hipError_t launch_iso_type(const FrameParams &P, const LaunchConfig &L, const IsoArgs &A, const void *vol, const float4 *tf,
                                   float4 *fb, uint32_t *spp, hipStream_t st)
 {
-    const int rows = launch_local_rows(P);
-    const unsigned tiles_x = (unsigned)((P.img_w + 15) / 16), tiles_y = (unsigned)((rows + 15) / 16);
-    const bool skip = A.skip_grid != nullptr;
-#define VR_ISO_L(LAY)                                                                                                              \
-    if (L.filter == 0) return skip ? launch_iso<VoxelT, LAY, 0, true>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st)             \
-                                   : launch_iso<VoxelT, LAY, 0, false>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);           \
-    return skip ? launch_iso<VoxelT, LAY, 1, true>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st)                                \
-                : launch_iso<VoxelT, LAY, 1, false>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
-    if (L.layout == 0) { VR_ISO_L(0) }
-    VR_ISO_L(1)
-#undef VR_ISO_L
+    const Tiles16 t = launch_tiles16(P);
+    const int div = texcoord_divmode(L);
+    const dim3 grid(padded_blocks(t.x, t.y)), block(256);
+    return dispatch_mode(L, BoolAxis{A.skip_grid != nullptr}, [&](auto LAY, auto FIL, auto SKIP, auto BIG) {
+        hipLaunchKernelGGL((raymarch_iso_kernel<VoxelT, LAY(), FIL(), SKIP(), BIG()>), grid, block, 0, st, P, div,
+                           BIG() ? 0u : (uint32_t)L.vol_bytes32, (const VoxelT *)vol, tf, fb, spp, A.depth, A.skip_grid, A.iso_s, t.x, t.y);
+        return hipGetLastError();
+    });
 }
+
+VR_CODE_UNIT(iso, VR_ISO_TU, "isosurface", WARM_LOAD_SHADER)
 
 #define VR_ISO_ARGS const FrameParams &P, const LaunchConfig &L, const IsoArgs &A, const void *vol, const float4 *tf, float4 *fb, uint32_t *spp, hipStream_t st
-#if VR_ISO_TU == 0 || VR_ISO_TU == -1
-hipError_t launch_iso_u8(VR_ISO_ARGS) { return launch_iso_type<uint8_t>(P, L, A, vol, tf, fb, spp, st); }
-#endif
-#if VR_ISO_TU == 1 || VR_ISO_TU == -1
+#if VR_ISO_TU == 1
 hipError_t launch_iso_u16(VR_ISO_ARGS) { return launch_iso_type<uint16_t>(P, L, A, vol, tf, fb, spp, st); }
-#endif
-
-// one empty kernel per unit: launching it makes the runtime inflate and load that unit's code object
-#if VR_ISO_TU >= 0
-#define VR_ISO_CAT2(a, b) a##b
-#define VR_ISO_CAT(a, b) VR_ISO_CAT2(a, b)
-__global__ void VR_ISO_CAT(warm_kernel_iso, VR_ISO_TU)() {}
-hipError_t VR_ISO_CAT(launch_warm_iso_tu, VR_ISO_TU)(hipStream_t st)
-{
-    hipLaunchKernelGGL(VR_ISO_CAT(warm_kernel_iso, VR_ISO_TU), dim3(1), dim3(64), 0, st);
-    return hipGetLastError();
-}
-#endif
-
-// the unit of 8-bit volumes also carries the entry points
-#if VR_ISO_TU == 0 || VR_ISO_TU == -1
-#if VR_ISO_TU == 0
+#else
+// the unit of 8-bit volumes also carries the entry point
 hipError_t launch_iso_u16(VR_ISO_ARGS);
-hipError_t launch_warm_iso_tu1(hipStream_t st);
-#endif
 
 hipError_t launch_raymarch_iso(VR_ISO_ARGS, const char **kernel_name)
 {
     if (kernel_name) *kernel_name = "raymarch_iso_kernel";
     if (launch_local_rows(P) <= 0 || P.img_w <= 0) return hipSuccess;
     if (!A.depth) return hipErrorInvalidValue;
-    return L.bytes_per_voxel == 1 ? launch_iso_u8(P, L, A, vol, tf, fb, spp, st) : launch_iso_u16(P, L, A, vol, tf, fb, spp, st);
-}
-
-hipError_t launch_warm_iso(hipStream_t st)
-{
-#if VR_ISO_TU == 0
-    hipError_t e = launch_warm_iso_tu0(st);
-    if (e == hipSuccess) e = launch_warm_iso_tu1(st);
-    return e;
-#else
-    (void)st;
-    return hipSuccess;
-#endif
+    return L.bytes_per_voxel == 1 ? launch_iso_type<uint8_t>(P, L, A, vol, tf, fb, spp, st) : launch_iso_u16(P, L, A, vol, tf, fb, spp, st);
 }
 #endif
 #undef VR_ISO_ARGS

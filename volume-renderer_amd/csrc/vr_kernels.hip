@@ -23,6 +23,7 @@
 
 #include <type_traits>
 
+#include "vr_code_unit.h"
 #include "vr_device.h"
 #include "vr_lds_dma.h"
 #include "vr_sampler.h"
@@ -30,10 +31,9 @@
 // Translation units: the ray-march kernels of one (voxel type, layout) pair are ~150 template
 // instances each, so the Makefile compiles this file five times in parallel:
 //   VR_TU = 0..3  ray-march kernels of (u8|u16) x (linear|bricked) + their dispatch
-//   VR_TU = -1    helper kernels, launchers and the top-level launch_raymarch
-//   VR_TU = -2    (default) everything in one translation unit
+//   VR_TU < 0     the main unit: helper kernels, launchers and the top-level launch_raymarch
 #ifndef VR_TU
-#define VR_TU -2
+#error "VR_TU: the unit number comes from the build"
 #endif
 #define VR_TU_MAIN (VR_TU < 0)
 
@@ -288,17 +288,8 @@ static hipError_t raymarch_tu(const FrameParams &P, const LaunchConfig &L, const
                : launch_generic<T, LAY, false>(P, L, vol, tf, fb, spp, tiles_x, tiles_y, st);
 }
 
-// one empty kernel per translation unit: launching it makes the runtime load that unit's code
-// object (vr_load_shader does this up front; a cold first ray-march launch costs ~16 ms otherwise)
-#if VR_TU >= 0
-#define VR_WARM_CAT2(a, b) a##b
-#define VR_WARM_CAT(a, b) VR_WARM_CAT2(a, b)
-__global__ void VR_WARM_CAT(warm_kernel_tu, VR_TU)() {}
-hipError_t VR_WARM_CAT(launch_warm_tu, VR_TU)(hipStream_t st)
-{
-    hipLaunchKernelGGL(VR_WARM_CAT(warm_kernel_tu, VR_TU), dim3(1), dim3(64), 0, st);
-    return hipGetLastError();
-}
+#if !VR_TU_MAIN
+VR_CODE_UNIT(tu, VR_TU, "ray march", WARM_LOAD_SHADER)
 #endif
 
 #define VR_TU_ARGS const FrameParams &P, const LaunchConfig &L, const void *vol, const float4 *tf, float4 *fb, uint32_t *spp, int rows, int fast, hipStream_t st
@@ -326,12 +317,10 @@ hipError_t launch_raymarch_slab_tri_u8(const FrameParams &P, const LaunchConfig 
 hipError_t launch_raymarch_slab_tri_u16(const FrameParams &P, const LaunchConfig &L, const void *vol, const float4 *tf, float4 *fb,
                                         uint32_t *spp, hipStream_t st);
 
-#if VR_TU == -1
 hipError_t launch_raymarch_tu0(VR_TU_ARGS);
 hipError_t launch_raymarch_tu1(VR_TU_ARGS);
 hipError_t launch_raymarch_tu2(VR_TU_ARGS);
 hipError_t launch_raymarch_tu3(VR_TU_ARGS);
-#endif
 
 hipError_t launch_raymarch(const FrameParams &P, const LaunchConfig &L, const void *vol, const float4 *tf,
                            float4 *fb, uint32_t *spp, hipStream_t st, const char **kernel_name)
@@ -348,42 +337,15 @@ hipError_t launch_raymarch(const FrameParams &P, const LaunchConfig &L, const vo
                                  : (fast == 2 ? "raymarch_tri_kernel"
                                               : (relay_selected(P, L) ? "raymarch_relay_kernel" : "raymarch_fast_kernel"));
     const int tu = (L.bytes_per_voxel == 1 ? 0 : 2) + (L.layout == 0 ? 0 : 1);
-#if VR_TU == -1
     switch (tu) {
     case 0: return launch_raymarch_tu0(P, L, vol, tf, fb, spp, rows, fast, st);
     case 1: return launch_raymarch_tu1(P, L, vol, tf, fb, spp, rows, fast, st);
     case 2: return launch_raymarch_tu2(P, L, vol, tf, fb, spp, rows, fast, st);
     default: return launch_raymarch_tu3(P, L, vol, tf, fb, spp, rows, fast, st);
     }
-#else
-    switch (tu) {
-    case 0: return raymarch_tu<uint8_t, 0>(P, L, vol, tf, fb, spp, rows, fast, st);
-    case 1: return raymarch_tu<uint8_t, 1>(P, L, vol, tf, fb, spp, rows, fast, st);
-    case 2: return raymarch_tu<uint16_t, 0>(P, L, vol, tf, fb, spp, rows, fast, st);
-    default: return raymarch_tu<uint16_t, 1>(P, L, vol, tf, fb, spp, rows, fast, st);
-    }
-#endif
 }
 
-__global__ void warm_kernel_main() {}
-#if VR_TU == -1
-hipError_t launch_warm_tu0(hipStream_t st);
-hipError_t launch_warm_tu1(hipStream_t st);
-hipError_t launch_warm_tu2(hipStream_t st);
-hipError_t launch_warm_tu3(hipStream_t st);
-#endif
-hipError_t launch_warm_modules(hipStream_t st)
-{
-    hipLaunchKernelGGL(warm_kernel_main, dim3(1), dim3(64), 0, st);
-    hipError_t e = hipGetLastError();
-#if VR_TU == -1
-    if (e == hipSuccess) e = launch_warm_tu0(st);
-    if (e == hipSuccess) e = launch_warm_tu1(st);
-    if (e == hipSuccess) e = launch_warm_tu2(st);
-    if (e == hipSuccess) e = launch_warm_tu3(st);
-#endif
-    return e;
-}
+VR_CODE_UNIT(main, , "ray march", WARM_LOAD_SHADER)
 
 #include "vr_helpers.hip"
 #endif  // VR_TU_MAIN

@@ -44,7 +44,4 @@ size_t mesh_scan_temp_bytes(uint64_t words);
 hipError_t launch_mesh_scan(uint64_t *scan, uint64_t words, void *temp, size_t temp_bytes, hipStream_t st);
 hipError_t launch_mesh_emit(const MeshSlab &S, hipStream_t st);
 
-// one empty launch per extraction translation unit: loads their code objects (vr_load_shader)
-hipError_t launch_warm_mesh(hipStream_t st);
-
 }  // namespace vr

@@ -15,14 +15,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vr_code_unit.h"
 #include "vr_frame.h"
 #include "vr_mesh.h"
 
 #ifndef VR_MESH_TU
-#define VR_MESH_TU -1
+#error "VR_MESH_TU: the unit number comes from the build"
 #endif
 
-#if VR_MESH_TU == 0 || VR_MESH_TU == -1
+#if VR_MESH_TU == 0
 #include <cstring>
 
 #include <rocprim/device/device_scan.hpp>
@@ -346,31 +347,14 @@ hipError_t launch_mesh_type(const MeshSlab &S, bool emit, hipStream_t st)
 
 }  // namespace
 
-#if VR_MESH_TU == 0 || VR_MESH_TU == -1
-hipError_t launch_mesh_u8(const MeshSlab &S, bool emit, hipStream_t st) { return launch_mesh_type<uint8_t>(S, emit, st); }
-#endif
-#if VR_MESH_TU == 1 || VR_MESH_TU == -1
+VR_CODE_UNIT(mesh, VR_MESH_TU, "extraction", WARM_LOAD_SHADER)
+
+#if VR_MESH_TU == 1
 hipError_t launch_mesh_u16(const MeshSlab &S, bool emit, hipStream_t st) { return launch_mesh_type<uint16_t>(S, emit, st); }
-#endif
-
-// one empty kernel per unit: launching it makes the runtime inflate and load that unit's code object
-#if VR_MESH_TU >= 0
-#define VR_MESH_CAT2(a, b) a##b
-#define VR_MESH_CAT(a, b) VR_MESH_CAT2(a, b)
-__global__ void VR_MESH_CAT(warm_kernel_mesh, VR_MESH_TU)() {}
-hipError_t VR_MESH_CAT(launch_warm_mesh_tu, VR_MESH_TU)(hipStream_t st)
-{
-    hipLaunchKernelGGL(VR_MESH_CAT(warm_kernel_mesh, VR_MESH_TU), dim3(1), dim3(64), 0, st);
-    return hipGetLastError();
-}
-#endif
-
+#else
 // the unit of 8-bit volumes also carries the entry points and the scan
-#if VR_MESH_TU == 0 || VR_MESH_TU == -1
-#if VR_MESH_TU == 0
+hipError_t launch_mesh_u8(const MeshSlab &S, bool emit, hipStream_t st) { return launch_mesh_type<uint8_t>(S, emit, st); }
 hipError_t launch_mesh_u16(const MeshSlab &S, bool emit, hipStream_t st);
-hipError_t launch_warm_mesh_tu1(hipStream_t st);
-#endif
 
 namespace {
 
@@ -410,18 +394,6 @@ hipError_t launch_mesh_scan(uint64_t *scan, uint64_t words, void *temp, size_t t
 {
     if (!scan || !temp || words == 0) return hipErrorInvalidValue;
     return rocprim::exclusive_scan(temp, temp_bytes, scan, scan, (uint64_t)0, (size_t)words, rocprim::plus<uint64_t>(), st);
-}
-
-hipError_t launch_warm_mesh(hipStream_t st)
-{
-#if VR_MESH_TU == 0
-    hipError_t e = launch_warm_mesh_tu0(st);
-    if (e == hipSuccess) e = launch_warm_mesh_tu1(st);
-    return e;
-#else
-    (void)st;
-    return hipSuccess;
-#endif
 }
 #endif
 

@@ -27,7 +27,4 @@ struct ResliceArgs {
 hipError_t launch_reslice(const FrameParams &P, const LaunchConfig &L, const ResliceArgs &A, const void *vol, const float4 *tf,
                           float4 *fb, uint32_t *spp, hipStream_t st, const char **kernel_name);
 
-// one empty launch per reslice translation unit: loads their code objects (vr_load_shader)
-hipError_t launch_warm_reslice(hipStream_t st);
-
 }  // namespace vr

@@ -4,7 +4,8 @@
 // in include/vr_core.h and DESIGN.md section 1; tests/reslice_ref/reslice_ref.c restates it on the CPU and
 // tests/test_reslice_gpu.py holds this kernel to it bit for bit.
 //
-// Its own translation units (VR_RESLICE_TU = 0: 8-bit volumes and the entry points, 1: 16-bit volumes), like vr_iso.hip: the
+// Its own translation units (VR_RESLICE_TU = 0: 8-bit volumes and the entry point, 1: 16-bit volumes; the build always sets it, and
+// VR_CODE_UNIT registers each for the pre-load), like vr_iso.hip; launched through mode_dispatch.h (MODE is its extra axis): the
 // vr_kernels.hip units, FrameParams and LaunchConfig are untouched by the mode; the plane, the slab and the values target
 // are extra kernel arguments.  Arithmetic contract as in vr_kernels.hip: one correctly rounded fp32 operation per step,
 // nothing contracted (-ffp-contract=off); the only fused operations are explicit: TRILINEAR's lerps (tri_lerp) and the
@@ -17,11 +18,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mode_dispatch.h"
+#include "vr_code_unit.h"
 #include "vr_sampler.h"
 #include "vr_reslice.h"
 
 #ifndef VR_RESLICE_TU
-#define VR_RESLICE_TU -1
+#error "VR_RESLICE_TU: the unit number comes from the build"
 #endif
 
 namespace vr {
@@ -103,89 +106,35 @@ __global__ __launch_bounds__(256) void reslice_kernel(const FrameParams P, const
     if (spp) spp[pix] = cnt;
 }
 
-template <typename VoxelT, int LAYOUT, int FILTER, int MODE>
-static hipError_t launch_rs(const FrameParams &P, const LaunchConfig &L, const ResliceArgs &A, const void *vol, const float4 *tf,
-                            float4 *fb, uint32_t *spp, unsigned tiles_x, unsigned tiles_y, hipStream_t st)
-{
-    const int div = L.divmode_win == DIV_CERT ? DIV_CERT : DIV_EXACT;
-    const dim3 grid(padded_blocks(tiles_x, tiles_y)), block(256);
-    if (L.big_offsets)
-        hipLaunchKernelGGL((reslice_kernel<VoxelT, LAYOUT, FILTER, MODE, true>), grid, block, 0, st, P, A.g, A.n, div, A.hu_offset, 0u,
-                           (const VoxelT *)vol, tf, fb, spp, A.values, tiles_x, tiles_y);
-    else
-        hipLaunchKernelGGL((reslice_kernel<VoxelT, LAYOUT, FILTER, MODE, false>), grid, block, 0, st, P, A.g, A.n, div, A.hu_offset,
-                           (uint32_t)L.vol_bytes32, (const VoxelT *)vol, tf, fb, spp, A.values, tiles_x, tiles_y);
-    return hipGetLastError();
-}
-
-template <typename VoxelT, int LAYOUT, int FILTER>
-static hipError_t launch_rs_mode(const FrameParams &P, const LaunchConfig &L, const ResliceArgs &A, const void *vol, const float4 *tf,
-                                 float4 *fb, uint32_t *spp, unsigned tiles_x, unsigned tiles_y, hipStream_t st)
-{
-    if (A.mode == 0) return launch_rs<VoxelT, LAYOUT, FILTER, 0>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
-    if (A.mode == 1) return launch_rs<VoxelT, LAYOUT, FILTER, 1>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
-    return launch_rs<VoxelT, LAYOUT, FILTER, 2>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
-}
-
 template <typename VoxelT>
 static hipError_t launch_rs_type(const FrameParams &P, const LaunchConfig &L, const ResliceArgs &A, const void *vol, const float4 *tf,
                                  float4 *fb, uint32_t *spp, hipStream_t st)
 {
-    const int rows = launch_local_rows(P);
-    const unsigned tiles_x = (unsigned)((P.img_w + 15) / 16), tiles_y = (unsigned)((rows + 15) / 16);
-    if (L.layout == 0) {
-        if (L.filter == 0) return launch_rs_mode<VoxelT, 0, 0>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
-        return launch_rs_mode<VoxelT, 0, 1>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
-    }
-    if (L.filter == 0) return launch_rs_mode<VoxelT, 1, 0>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
-    return launch_rs_mode<VoxelT, 1, 1>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
+    const Tiles16 t = launch_tiles16(P);
+    const int div = window_divmode(L);
+    const dim3 grid(padded_blocks(t.x, t.y)), block(256);
+    return dispatch_mode(L, IntAxis<3>{A.mode}, [&](auto LAY, auto FIL, auto MODE, auto BIG) {
+        hipLaunchKernelGGL((reslice_kernel<VoxelT, LAY(), FIL(), MODE(), BIG()>), grid, block, 0, st, P, A.g, A.n, div, A.hu_offset,
+                           BIG() ? 0u : (uint32_t)L.vol_bytes32, (const VoxelT *)vol, tf, fb, spp, A.values, t.x, t.y);
+        return hipGetLastError();
+    });
 }
+
+VR_CODE_UNIT(reslice, VR_RESLICE_TU, "reslice", WARM_LOAD_SHADER)
 
 #define VR_RESLICE_ARGS const FrameParams &P, const LaunchConfig &L, const ResliceArgs &A, const void *vol, const float4 *tf, float4 *fb, uint32_t *spp, hipStream_t st
-#if VR_RESLICE_TU == 0 || VR_RESLICE_TU == -1
-hipError_t launch_reslice_u8(VR_RESLICE_ARGS) { return launch_rs_type<uint8_t>(P, L, A, vol, tf, fb, spp, st); }
-#endif
-#if VR_RESLICE_TU == 1 || VR_RESLICE_TU == -1
+#if VR_RESLICE_TU == 1
 hipError_t launch_reslice_u16(VR_RESLICE_ARGS) { return launch_rs_type<uint16_t>(P, L, A, vol, tf, fb, spp, st); }
-#endif
-
-// one empty kernel per unit: launching it makes the runtime inflate and load that unit's code object
-#if VR_RESLICE_TU >= 0
-#define VR_RESLICE_CAT2(a, b) a##b
-#define VR_RESLICE_CAT(a, b) VR_RESLICE_CAT2(a, b)
-__global__ void VR_RESLICE_CAT(warm_kernel_reslice, VR_RESLICE_TU)() {}
-hipError_t VR_RESLICE_CAT(launch_warm_reslice_tu, VR_RESLICE_TU)(hipStream_t st)
-{
-    hipLaunchKernelGGL(VR_RESLICE_CAT(warm_kernel_reslice, VR_RESLICE_TU), dim3(1), dim3(64), 0, st);
-    return hipGetLastError();
-}
-#endif
-
-// the unit of 8-bit volumes also carries the entry points
-#if VR_RESLICE_TU == 0 || VR_RESLICE_TU == -1
-#if VR_RESLICE_TU == 0
+#else
+// the unit of 8-bit volumes also carries the entry point
 hipError_t launch_reslice_u16(VR_RESLICE_ARGS);
-hipError_t launch_warm_reslice_tu1(hipStream_t st);
-#endif
 
 hipError_t launch_reslice(VR_RESLICE_ARGS, const char **kernel_name)
 {
     if (kernel_name) *kernel_name = "reslice_kernel";
     if (launch_local_rows(P) <= 0 || P.img_w <= 0) return hipSuccess;
     if (!A.values || A.n < 1 || A.n > 1024 || A.mode < 0 || A.mode > 2) return hipErrorInvalidValue;
-    return L.bytes_per_voxel == 1 ? launch_reslice_u8(P, L, A, vol, tf, fb, spp, st) : launch_reslice_u16(P, L, A, vol, tf, fb, spp, st);
-}
-
-hipError_t launch_warm_reslice(hipStream_t st)
-{
-#if VR_RESLICE_TU == 0
-    hipError_t e = launch_warm_reslice_tu0(st);
-    if (e == hipSuccess) e = launch_warm_reslice_tu1(st);
-    return e;
-#else
-    (void)st;
-    return hipSuccess;
-#endif
+    return L.bytes_per_voxel == 1 ? launch_rs_type<uint8_t>(P, L, A, vol, tf, fb, spp, st) : launch_reslice_u16(P, L, A, vol, tf, fb, spp, st);
 }
 #endif
 #undef VR_RESLICE_ARGS

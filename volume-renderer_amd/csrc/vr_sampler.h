@@ -1,6 +1,7 @@
 // vr_sampler.h -- the volume sampler and the per-pixel scaffold shared by the one-pixel-per-lane kernels on 16x16-pixel tiles
 // (vr_generic.hip, vr_iso.hip, vr_reslice.hip, vr_shade.hip): the tile-to-pixel mapping, NEAREST and TRILINEAR fetches, the texture
-// coordinates, the window map and the transfer-function index.  Arithmetic contract as in vr_kernels.hip.
+// coordinates, the window map and the transfer-function index.  Arithmetic contract as in vr_kernels.hip.  What only the
+// isosurface and the shading kernel share (ray start, skip cell) is in vr_march.h; their launch scaffold is mode_dispatch.h.
 #pragma once
 #include "vr_device.h"
 
@@ -106,8 +107,8 @@ struct VolumeSampler {
     }
 };
 
-// cartesianToTextureCoord (VolumeRenderer.cs:175-192): box position q -> texture coordinates.  The generic and the shading
-// kernel keep the same lines inline in their loops: called from there, this function changes their compiled code.
+// cartesianToTextureCoord (VolumeRenderer.cs:175-192): box position q -> texture coordinates (generic and isosurface kernels).
+// The shading kernel keeps the same lines inline in its loop: called from there, this function changes its compiled code.
 __device__ __forceinline__ void texcoord(const FrameParams &P, int divmode, float qx, float qy, float qz, float &tcx, float &tcy, float &tcz)
 {
     float ux = qx + P.half[0], uy = qy + P.half[1], uz = qz + P.half[2];

@@ -20,7 +20,4 @@ struct ShadeArgs {
 hipError_t launch_raymarch_shade(const FrameParams &P, const LaunchConfig &L, const ShadeArgs &A, const void *vol, const float4 *tf,
                                  float4 *fb, uint32_t *spp, hipStream_t st, const char **kernel_name);
 
-// one empty launch per shading translation unit: loads their code objects (vr_load_shader)
-hipError_t launch_warm_shade(hipStream_t st);
-
 }  // namespace vr

@@ -3,7 +3,8 @@
 // headlight.  The definition, step by step, is in include/vr_core.h and DESIGN.md section 1.3; tests/shade_ref/shade_ref.c
 // restates it on the CPU and tests/test_shading_gpu.py holds this kernel to it bit for bit.
 //
-// Its own translation units (VR_SHADE_TU = 0: 8-bit volumes, 1: 16-bit volumes), like vr_iso.hip: the vr_kernels.hip units,
+// Its own translation units (VR_SHADE_TU = 0: 8-bit volumes and the entry point, 1: 16-bit volumes; the build always sets it, and
+// VR_CODE_UNIT registers each for the pre-load), like vr_iso.hip; launched through mode_dispatch.h: the vr_kernels.hip units,
 // FrameParams and LaunchConfig are untouched by the mode; the coefficients and the skip grid are extra kernel arguments.
 // Arithmetic contract as in vr_kernels.hip: one correctly rounded fp32 operation per step, nothing contracted
 // (-ffp-contract=off), the only fused operations are explicit: TRILINEAR's lerps (tri_lerp) and the certified divisions
@@ -18,14 +19,17 @@
 // so a sample in a cell whose DILATED maximum is <= the threshold (RendererCore::zeroAlphaThreshold) classifies to alpha 0 and
 // is not fetched: it would add +-0 to dest, which is never -0.  Positions still advance sample by sample and every step is
 // counted, so frames and counts are the same bits with and without it.
+// The ray start and the skip cell are vr_march.h's, shared with vr_iso.hip; gradient, normal and headlight are written out here.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "vr_sampler.h"
+#include "mode_dispatch.h"
+#include "vr_code_unit.h"
+#include "vr_march.h"
 #include "vr_shade.h"
 
 #ifndef VR_SHADE_TU
-#define VR_SHADE_TU -1
+#error "VR_SHADE_TU: the unit number comes from the build"
 #endif
 
 namespace vr {
@@ -55,20 +59,15 @@ __global__ __launch_bounds__(256) void raymarch_shade_kernel(const FrameParams P
     uint32_t fetches = 0;
     if (intersect_ray_aabb(P, ray, t_min, t_max)) {
         const VolumeSampler<VoxelT, LAYOUT, BIG> S(P, vol, vol_bytes);
-        auto nearest_index = [&](float tc, float fdim, int n) -> int { return clampi(floor_to_int_sat(tc * fdim), 0, n - 1); };
-
-        const float EPSILON = 0.000001f;
-        const float sx = ray.ox + ray.dx * t_min, sy = ray.oy + ray.dy * t_min, sz = ray.oz + ray.dz * t_min;
-        const float p0x = sx + ray.dx * EPSILON, p0y = sy + ray.dy * EPSILON, p0z = sz + ray.dz * EPSILON;
-        const float dsx = ray.dx * P.step, dsy = ray.dy * P.step, dsz = ray.dz * P.step;
+        const RayStart R = ray_start(P, ray, t_min);
+        const float p0x = R.p0x, p0y = R.p0y, p0z = R.p0z, dsx = R.dsx, dsy = R.dsy, dsz = R.dsz;
         // the headlight L = V = H = -dir, and the box-space scale of each volume axis (dim / ext, the view's permutation)
         const float lx_ = -ray.dx, ly_ = -ray.dy, lz_ = -ray.dz;
         const float gsx = P.fdim[0] / P.ext[0];
         const float gsy = (P.view_top == 1 || P.view_bottom == 1) ? P.fdim[2] / P.ext[1] : P.fdim[1] / P.ext[1];
         const float gsz = (P.view_top == 1 || P.view_bottom == 1) ? P.fdim[1] / P.ext[2] : P.fdim[2] / P.ext[2];
         float qx = p0x, qy = p0y, qz = p0z;
-        uint32_t cell = 0xffffffffu;
-        bool cell_empty = false;
+        SkipCell skip;
         for (int i = 0; i < P.max_steps; i++) {
             if (P.accum == 1) {
                 const float fi = (float)i;
@@ -98,16 +97,11 @@ __global__ __launch_bounds__(256) void raymarch_shade_kernel(const FrameParams P
                 vi = nearest_index(tcx, P.fdim[0], P.nx); vj = nearest_index(tcy, P.fdim[1], P.ny); vk = nearest_index(tcz, P.fdim[2], P.nz);
             } else {
                 u = tcx * P.fdim[0] - 0.5f; v = tcy * P.fdim[1] - 0.5f; w = tcz * P.fdim[2] - 0.5f;
-                vi = clampi((int)floorf(u), 0, P.nx - 1); vj = clampi((int)floorf(v), 0, P.ny - 1); vk = clampi((int)floorf(w), 0, P.nz - 1);
+                vi = lower_tap(u, P.nx); vj = lower_tap(v, P.ny); vk = lower_tap(w, P.nz);
             }
             bool visible = true;
             if (SKIP) {
-                const uint32_t c = ((uint32_t)vi >> 3) + (uint32_t)P.cnx * (((uint32_t)vj >> 3) + (uint32_t)P.cny * ((uint32_t)vk >> 3));
-                if (c != cell) {
-                    cell = c;
-                    cell_empty = (int32_t)grid[c] <= skip_thresh;
-                }
-                visible = !cell_empty;
+                visible = !skip.enter(P, grid, vi, vj, vk, [&](uint16_t cell_max) { return (int32_t)cell_max <= skip_thresh; });
             }
             if (visible) {
                 float s = FILTER == 0 ? S.voxel(vi, vj, vk) : S.trilinear(u, v, w);
@@ -171,86 +165,36 @@ __global__ __launch_bounds__(256) void raymarch_shade_kernel(const FrameParams P
     if (spp) spp[pix] = fetches;
 }
 
-template <typename VoxelT, int LAYOUT, int FILTER, bool SKIP>
-static hipError_t launch_shade(const FrameParams &P, const LaunchConfig &L, const ShadeArgs &A, const void *vol, const float4 *tf,
-                               float4 *fb, uint32_t *spp, unsigned tiles_x, unsigned tiles_y, hipStream_t st)
-{
-    const int div = L.divmode_tc == DIV_EXACT ? DIV_EXACT : DIV_CERT;
-    const int div_win = L.divmode_win == DIV_CERT ? DIV_CERT : DIV_EXACT;
-    const dim3 grid(padded_blocks(tiles_x, tiles_y)), block(256);
-    if (L.big_offsets)
-        hipLaunchKernelGGL((raymarch_shade_kernel<VoxelT, LAYOUT, FILTER, SKIP, true>), grid, block, 0, st, P, div, div_win, 0u,
-                           (const VoxelT *)vol, tf, fb, spp, A.skip_grid, A.skip_thresh, A.ambient, A.diffuse, A.specular,
-                           A.spec_squarings, tiles_x, tiles_y);
-    else
-        hipLaunchKernelGGL((raymarch_shade_kernel<VoxelT, LAYOUT, FILTER, SKIP, false>), grid, block, 0, st, P, div, div_win,
-                           (uint32_t)L.vol_bytes32, (const VoxelT *)vol, tf, fb, spp, A.skip_grid, A.skip_thresh, A.ambient, A.diffuse,
-                           A.specular, A.spec_squarings, tiles_x, tiles_y);
-    return hipGetLastError();
-}
-
 template <typename VoxelT>
 static hipError_t launch_shade_type(const FrameParams &P, const LaunchConfig &L, const ShadeArgs &A, const void *vol, const float4 *tf,
                                     float4 *fb, uint32_t *spp, hipStream_t st)
 {
-    const int rows = launch_local_rows(P);
-    const unsigned tiles_x = (unsigned)((P.img_w + 15) / 16), tiles_y = (unsigned)((rows + 15) / 16);
-    const bool skip = A.skip_grid != nullptr;
-#define VR_SHADE_L(LAY)                                                                                                            \
-    if (L.filter == 0) return skip ? launch_shade<VoxelT, LAY, 0, true>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st)           \
-                                   : launch_shade<VoxelT, LAY, 0, false>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);         \
-    return skip ? launch_shade<VoxelT, LAY, 1, true>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st)                              \
-                : launch_shade<VoxelT, LAY, 1, false>(P, L, A, vol, tf, fb, spp, tiles_x, tiles_y, st);
-    if (L.layout == 0) { VR_SHADE_L(0) }
-    VR_SHADE_L(1)
-#undef VR_SHADE_L
+    const Tiles16 t = launch_tiles16(P);
+    const int div = texcoord_divmode(L), div_win = window_divmode(L);
+    const dim3 grid(padded_blocks(t.x, t.y)), block(256);
+    return dispatch_mode(L, BoolAxis{A.skip_grid != nullptr}, [&](auto LAY, auto FIL, auto SKIP, auto BIG) {
+        hipLaunchKernelGGL((raymarch_shade_kernel<VoxelT, LAY(), FIL(), SKIP(), BIG()>), grid, block, 0, st, P, div, div_win,
+                           BIG() ? 0u : (uint32_t)L.vol_bytes32, (const VoxelT *)vol, tf, fb, spp, A.skip_grid, A.skip_thresh, A.ambient,
+                           A.diffuse, A.specular, A.spec_squarings, t.x, t.y);
+        return hipGetLastError();
+    });
 }
+
+VR_CODE_UNIT(shade, VR_SHADE_TU, "shading", WARM_LOAD_SHADER)
 
 #define VR_SHADE_ARGS const FrameParams &P, const LaunchConfig &L, const ShadeArgs &A, const void *vol, const float4 *tf, float4 *fb, uint32_t *spp, hipStream_t st
-#if VR_SHADE_TU == 0 || VR_SHADE_TU == -1
-hipError_t launch_shade_u8(VR_SHADE_ARGS) { return launch_shade_type<uint8_t>(P, L, A, vol, tf, fb, spp, st); }
-#endif
-#if VR_SHADE_TU == 1 || VR_SHADE_TU == -1
+#if VR_SHADE_TU == 1
 hipError_t launch_shade_u16(VR_SHADE_ARGS) { return launch_shade_type<uint16_t>(P, L, A, vol, tf, fb, spp, st); }
-#endif
-
-// one empty kernel per unit: launching it makes the runtime inflate and load that unit's code object
-#if VR_SHADE_TU >= 0
-#define VR_SHADE_CAT2(a, b) a##b
-#define VR_SHADE_CAT(a, b) VR_SHADE_CAT2(a, b)
-__global__ void VR_SHADE_CAT(warm_kernel_shade, VR_SHADE_TU)() {}
-hipError_t VR_SHADE_CAT(launch_warm_shade_tu, VR_SHADE_TU)(hipStream_t st)
-{
-    hipLaunchKernelGGL(VR_SHADE_CAT(warm_kernel_shade, VR_SHADE_TU), dim3(1), dim3(64), 0, st);
-    return hipGetLastError();
-}
-#endif
-
-// the unit of 8-bit volumes also carries the entry points
-#if VR_SHADE_TU == 0 || VR_SHADE_TU == -1
-#if VR_SHADE_TU == 0
+#else
+// the unit of 8-bit volumes also carries the entry point
 hipError_t launch_shade_u16(VR_SHADE_ARGS);
-hipError_t launch_warm_shade_tu1(hipStream_t st);
-#endif
 
 hipError_t launch_raymarch_shade(VR_SHADE_ARGS, const char **kernel_name)
 {
     if (kernel_name) *kernel_name = "raymarch_shade_kernel";
     if (launch_local_rows(P) <= 0 || P.img_w <= 0) return hipSuccess;
     if (P.tf_len > 256 || (P.tf_len > 1 && !tf) || A.spec_squarings < 0 || A.spec_squarings > 7) return hipErrorInvalidValue;
-    return L.bytes_per_voxel == 1 ? launch_shade_u8(P, L, A, vol, tf, fb, spp, st) : launch_shade_u16(P, L, A, vol, tf, fb, spp, st);
-}
-
-hipError_t launch_warm_shade(hipStream_t st)
-{
-#if VR_SHADE_TU == 0
-    hipError_t e = launch_warm_shade_tu0(st);
-    if (e == hipSuccess) e = launch_warm_shade_tu1(st);
-    return e;
-#else
-    (void)st;
-    return hipSuccess;
-#endif
+    return L.bytes_per_voxel == 1 ? launch_shade_type<uint8_t>(P, L, A, vol, tf, fb, spp, st) : launch_shade_u16(P, L, A, vol, tf, fb, spp, st);
 }
 #endif
 #undef VR_SHADE_ARGS

@@ -48,7 +48,4 @@ hipError_t launch_simplify_emit_vertices(const float *positions, const float *no
 hipError_t launch_simplify_emit_triangles(const uint32_t *triangles, const uint32_t *triangle_offset, uint64_t nt, const uint32_t *rep,
                                           const uint32_t *vertex_offset, uint32_t *out_triangles, hipStream_t st);
 
-// one empty launch: loads the unit's code object (vr_load_shader)
-hipError_t launch_warm_simplify(hipStream_t st);
-
 }  // namespace vr

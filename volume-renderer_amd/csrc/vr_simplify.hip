@@ -24,6 +24,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "vr_code_unit.h"
 #include "vr_simplify.h"
 
 namespace vr {
@@ -192,8 +193,6 @@ __global__ __launch_bounds__(256) void simplify_emit_triangles_kernel(const uint
     out[3ull * o + (g - 3 * t)] = vertex_offset[rep[tri[g]]];
 }
 
-__global__ void warm_kernel_simplify() {}
-
 }  // namespace
 
 hipError_t launch_simplify_extent(const float *positions, uint64_t nv, float cell, uint32_t *stats4, hipStream_t st)
@@ -327,10 +326,8 @@ hipError_t launch_simplify_emit_triangles(const uint32_t *triangles, const uint3
     return hipGetLastError();
 }
 
-hipError_t launch_warm_simplify(hipStream_t st)
-{
-    hipLaunchKernelGGL(warm_kernel_simplify, dim3(1), dim3(64), 0, st);
-    return hipGetLastError();
-}
+namespace {
+VR_CODE_UNIT(simplify, , "simplification", WARM_LOAD_SHADER)
+}  // namespace
 
 }  // namespace vr

@@ -33,7 +33,4 @@ struct SmoothPass {
 };
 hipError_t launch_smooth_pass(const SmoothPass &S, hipStream_t st);
 
-// one empty launch per smoothing translation unit: loads their code objects (vr_load_shader)
-hipError_t launch_warm_smooth(hipStream_t st);
-
 }  // namespace vr

@@ -23,11 +23,12 @@
 
 #include <cmath>
 
+#include "vr_code_unit.h"
 #include "vr_frame.h"
 #include "vr_smooth.h"
 
 #ifndef VR_SMOOTH_TU
-#define VR_SMOOTH_TU -1
+#error "VR_SMOOTH_TU: the unit number comes from the build"
 #endif
 
 namespace vr {
@@ -265,31 +266,14 @@ hipError_t launch_smooth_type(const SmoothPass &S, hipStream_t st)
 
 }  // namespace
 
-#if VR_SMOOTH_TU == 0 || VR_SMOOTH_TU == -1
-hipError_t launch_smooth_u8(const SmoothPass &S, hipStream_t st) { return launch_smooth_type<uint8_t>(S, st); }
-#endif
-#if VR_SMOOTH_TU == 1 || VR_SMOOTH_TU == -1
+VR_CODE_UNIT(smooth, VR_SMOOTH_TU, "smoothing", WARM_LOAD_SHADER)
+
+#if VR_SMOOTH_TU == 1
 hipError_t launch_smooth_u16(const SmoothPass &S, hipStream_t st) { return launch_smooth_type<uint16_t>(S, st); }
-#endif
-
-// one empty kernel per unit: launching it makes the runtime inflate and load that unit's code object
-#if VR_SMOOTH_TU >= 0
-#define VR_SMOOTH_CAT2(a, b) a##b
-#define VR_SMOOTH_CAT(a, b) VR_SMOOTH_CAT2(a, b)
-__global__ void VR_SMOOTH_CAT(warm_kernel_smooth, VR_SMOOTH_TU)() {}
-hipError_t VR_SMOOTH_CAT(launch_warm_smooth_tu, VR_SMOOTH_TU)(hipStream_t st)
-{
-    hipLaunchKernelGGL(VR_SMOOTH_CAT(warm_kernel_smooth, VR_SMOOTH_TU), dim3(1), dim3(64), 0, st);
-    return hipGetLastError();
-}
-#endif
-
+#else
 // the unit of 8-bit volumes also carries the entry points
-#if VR_SMOOTH_TU == 0 || VR_SMOOTH_TU == -1
-#if VR_SMOOTH_TU == 0
+hipError_t launch_smooth_u8(const SmoothPass &S, hipStream_t st) { return launch_smooth_type<uint8_t>(S, st); }
 hipError_t launch_smooth_u16(const SmoothPass &S, hipStream_t st);
-hipError_t launch_warm_smooth_tu1(hipStream_t st);
-#endif
 
 bool smooth_weights(float sigma, float *w, int capacity, int *radius)
 {
@@ -320,18 +304,6 @@ hipError_t launch_smooth_pass(const SmoothPass &S, hipStream_t st)
     if (S.in_float && (S.in_planes < 1 || lo < S.in_z0 || hi > S.in_z0 + S.in_planes)) return hipErrorInvalidValue;
     if (S.out_float && (S.out_planes < 1 || S.z_begin < S.out_z0 || S.z_end > S.out_z0 + S.out_planes)) return hipErrorInvalidValue;
     return S.bytes_per_voxel == 1 ? launch_smooth_u8(S, st) : launch_smooth_u16(S, st);
-}
-
-hipError_t launch_warm_smooth(hipStream_t st)
-{
-#if VR_SMOOTH_TU == 0
-    hipError_t e = launch_warm_smooth_tu0(st);
-    if (e == hipSuccess) e = launch_warm_smooth_tu1(st);
-    return e;
-#else
-    (void)st;
-    return hipSuccess;
-#endif
 }
 #endif
 

@@ -47,6 +47,5 @@ hipError_t launch_stream_record(const FrameParams &P, const LaunchConfig &L, con
 // a frame from the stream: classification and compositing of every recorded sample (the fast kernel's modes; needs L.tile_table)
 hipError_t launch_raymarch_stream(const FrameParams &P, const LaunchConfig &L, const float4 *tf, float4 *fb, const RayStreamView &S,
                                   hipStream_t st, const char **kernel_name);
-hipError_t launch_warm_stream(hipStream_t st);   // one empty launch per translation unit of vr_stream.hip
 
 }  // namespace vr

@@ -26,12 +26,13 @@
 
 #include <type_traits>
 
+#include "vr_code_unit.h"
 #include "vr_device.h"
 #include "vr_lds_dma.h"
 #include "vr_stream.h"
 
 #ifndef VR_STREAM_TU
-#define VR_STREAM_TU -1
+#error "VR_STREAM_TU: the unit number comes from the build"
 #endif
 // groups of G samples a lane keeps in flight beyond the ones it composites, and plain (0) or non-temporal (1) stream loads:
 // measured alternatives in docs/lab-notebook.md, "Ray-ordered sample stream: first measurements"
@@ -524,14 +525,8 @@ static hipError_t launch_replay_type(const FrameParams &P, const LaunchConfig &L
     return launch_replay_mode<VoxelT, 0, PACK>(P, L, tf, fb, S, st);
 }
 
-#if VR_STREAM_TU == 2 || VR_STREAM_TU == -1
+#if VR_STREAM_TU == 2
 // the packed format's instances (16-bit volumes)
-__global__ void warm_kernel_stream_p12() {}
-hipError_t launch_warm_stream_p12(hipStream_t st)
-{
-    hipLaunchKernelGGL(warm_kernel_stream_p12, dim3(1), dim3(64), 0, st);
-    return hipGetLastError();
-}
 hipError_t launch_stream_record_p12(const FrameParams &P, const LaunchConfig &L, const void *vol, uint16_t *counts, const uint64_t *offsets,
                                     void *samples, int base, hipStream_t st)
 {
@@ -545,13 +540,7 @@ hipError_t launch_raymarch_stream_p12(const FrameParams &P, const LaunchConfig &
 }
 #endif
 
-#if VR_STREAM_TU == 1 || VR_STREAM_TU == -1
-__global__ void warm_kernel_stream_u16() {}
-hipError_t launch_warm_stream_u16(hipStream_t st)
-{
-    hipLaunchKernelGGL(warm_kernel_stream_u16, dim3(1), dim3(64), 0, st);
-    return hipGetLastError();
-}
+#if VR_STREAM_TU == 1
 hipError_t launch_stream_record_u16(const FrameParams &P, const LaunchConfig &L, const void *vol, uint16_t *counts, uint32_t *block_elems,
                                     const uint64_t *offsets, void *samples, hipStream_t st)
 {
@@ -563,12 +552,10 @@ hipError_t launch_raymarch_stream_u16(const FrameParams &P, const LaunchConfig &
 }
 #endif
 
-#if VR_STREAM_TU == 0 || VR_STREAM_TU == -1
-hipError_t launch_warm_stream_u16(hipStream_t st);
+#if VR_STREAM_TU == 0
 hipError_t launch_stream_record_u16(const FrameParams &P, const LaunchConfig &L, const void *vol, uint16_t *counts, uint32_t *block_elems,
                                     const uint64_t *offsets, void *samples, hipStream_t st);
 hipError_t launch_raymarch_stream_u16(const FrameParams &P, const LaunchConfig &L, const float4 *tf, float4 *fb, const RayStreamView &S, hipStream_t st);
-hipError_t launch_warm_stream_p12(hipStream_t st);
 hipError_t launch_stream_record_p12(const FrameParams &P, const LaunchConfig &L, const void *vol, uint16_t *counts, const uint64_t *offsets,
                                     void *samples, int base, hipStream_t st);
 hipError_t launch_raymarch_stream_p12(const FrameParams &P, const LaunchConfig &L, const float4 *tf, float4 *fb, const RayStreamView &S, hipStream_t st);
@@ -648,15 +635,8 @@ hipError_t launch_raymarch_stream(const FrameParams &P, const LaunchConfig &L, c
     if (kernel_name) *kernel_name = "raymarch_stream_kernel";
     return L.bytes_per_voxel == 1 ? launch_replay_type<uint8_t>(P, L, tf, fb, S, st) : launch_raymarch_stream_u16(P, L, tf, fb, S, st);
 }
-
-__global__ void warm_kernel_stream_u8() {}
-hipError_t launch_warm_stream(hipStream_t st)
-{
-    hipLaunchKernelGGL(warm_kernel_stream_u8, dim3(1), dim3(64), 0, st);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = launch_warm_stream_u16(st);
-    return e == hipSuccess ? launch_warm_stream_p12(st) : e;
-}
 #endif
+
+VR_CODE_UNIT(stream, VR_STREAM_TU, "sample stream", WARM_LOAD_SHADER)
 
 }  // namespace vr

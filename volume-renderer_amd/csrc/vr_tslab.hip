@@ -50,6 +50,7 @@
 // No MFMA: eight taps, seven lerps and a 5-flop recurrence per sample.
 #include <cstdlib>
 
+#include "vr_code_unit.h"
 #include "vr_device.h"
 #include "vr_lds_dma.h"
 
@@ -1294,9 +1295,9 @@ hipError_t launch_tslab_u16_small(VR_TSLAB_ARGS);
 hipError_t launch_tslab_u16_smallperm(VR_TSLAB_ARGS);
 
 #ifndef VR_TSLAB_TU
-#define VR_TSLAB_TU -1
+#error "VR_TSLAB_TU: the unit number comes from the build"
 #endif
-#if VR_TSLAB_TU == 0 || VR_TSLAB_TU == -1
+#if VR_TSLAB_TU == 0
 hipError_t launch_raymarch_slab_tri_u8(VR_TSLAB_ARGS)
 {
     if (L.tri_slab == 4 && L.tile_table_tall != nullptr) return launch_tslab_u8_tall(P, L, vol, tf, fb, spp, st);
@@ -1305,7 +1306,7 @@ hipError_t launch_raymarch_slab_tri_u8(VR_TSLAB_ARGS)
     return dispatch_tslab<uint8_t, 8, 80, false>(P, L, vol, tf, fb, spp, st);
 }
 #endif
-#if VR_TSLAB_TU == 1 || VR_TSLAB_TU == -1
+#if VR_TSLAB_TU == 1
 hipError_t launch_raymarch_slab_tri_u16(VR_TSLAB_ARGS)
 {
     const bool perm_ok = L.apron_y != nullptr && L.apron_x != nullptr;
@@ -1317,19 +1318,19 @@ hipError_t launch_raymarch_slab_tri_u16(VR_TSLAB_ARGS)
     return dispatch_tslab<uint16_t, 8, 80, false>(P, L, vol, tf, fb, spp, st);
 }
 #endif
-#if VR_TSLAB_TU == 2 || VR_TSLAB_TU == -1
+#if VR_TSLAB_TU == 2
 hipError_t launch_tslab_u16_half(VR_TSLAB_ARGS) { return dispatch_tslab<uint16_t, 8, 80, true>(P, L, vol, tf, fb, spp, st); }
 #endif
-#if VR_TSLAB_TU == 3 || VR_TSLAB_TU == -1
+#if VR_TSLAB_TU == 3
 hipError_t launch_tslab_u16_halftall(VR_TSLAB_ARGS) { return dispatch_tslab<uint16_t, 8, 80, true, 2>(P, L, vol, tf, fb, spp, st); }
 #endif
-#if VR_TSLAB_TU == 4 || VR_TSLAB_TU == -1
+#if VR_TSLAB_TU == 4
 hipError_t launch_tslab_u8_tall(VR_TSLAB_ARGS) { return dispatch_tslab<uint8_t, 8, 80, false, 2>(P, L, vol, tf, fb, spp, st); }
 #endif
-#if VR_TSLAB_TU == 5 || VR_TSLAB_TU == -1
+#if VR_TSLAB_TU == 5
 hipError_t launch_tslab_u16_three(VR_TSLAB_ARGS) { return dispatch_tslab<uint16_t, 8, 53, false>(P, L, vol, tf, fb, spp, st); }
 #endif
-#if VR_TSLAB_TU == 6 || VR_TSLAB_TU == -1
+#if VR_TSLAB_TU == 6
 hipError_t launch_tslab_u8_three(VR_TSLAB_ARGS) { return dispatch_tslab<uint8_t, 8, 53, false>(P, L, vol, tf, fb, spp, st); }
 #endif
 // round 6: 16x16-pixel tiles on FOUR wavefronts and 40 KiB, four workgroups per CU (tri_slab 6): what pays where a tile's brick layers are
@@ -1338,56 +1339,18 @@ hipError_t launch_tslab_u8_three(VR_TSLAB_ARGS) { return dispatch_tslab<uint8_t,
 // a 1024^3 volume's layers do not fit 40 KiB three deep (default pose 1.12 -> 1.22 ms, off-axis 1.55 -> 2.74: 40 % of the tiles on global
 // taps), so the work model offers the shape only below that size.  (Measured and dropped: the same tiles on 26 KiB, six workgroups per
 // CU at 80 VGPRs -- cfg1 0.1175 vs 0.1186 ms, cfg2 0.3808 vs 0.3810: nothing for another translation unit.)
-#if VR_TSLAB_TU == 7 || VR_TSLAB_TU == -1
+#if VR_TSLAB_TU == 7
 hipError_t launch_tslab_u8_small(VR_TSLAB_ARGS) { return dispatch_tslab<uint8_t, 4, 40, false, 2>(P, L, vol, tf, fb, spp, st); }
 #endif
-#if VR_TSLAB_TU == 8 || VR_TSLAB_TU == -1
+#if VR_TSLAB_TU == 8
 hipError_t launch_tslab_u16_small(VR_TSLAB_ARGS) { return dispatch_tslab<uint16_t, 4, 40, false, 2>(P, L, vol, tf, fb, spp, st); }
 #endif
-#if VR_TSLAB_TU == 9 || VR_TSLAB_TU == -1
+#if VR_TSLAB_TU == 9
 hipError_t launch_tslab_u16_smallperm(VR_TSLAB_ARGS) { return dispatch_tslab<uint16_t, 4, 40, true, 2>(P, L, vol, tf, fb, spp, st); }
 #endif
 
-// one empty kernel per translation unit (like vr_kernels.hip's warm_kernel_*): launching it makes the runtime inflate and
-// load that unit's code object.  launch_warm_tslab() touches all ten when TRILINEAR is selected (vr_set_filter /
-// vr_load_shader), so neither the first TRILINEAR frame nor the first frame of a shape the measured choice tries pays it.
-#if VR_TSLAB_TU >= 0
-#define VR_TSLAB_CAT2(a, b) a##b
-#define VR_TSLAB_CAT(a, b) VR_TSLAB_CAT2(a, b)
-__global__ void VR_TSLAB_CAT(warm_kernel_tslab, VR_TSLAB_TU)() {}
-hipError_t VR_TSLAB_CAT(launch_warm_tslab_tu, VR_TSLAB_TU)(hipStream_t st)
-{
-    hipLaunchKernelGGL(VR_TSLAB_CAT(warm_kernel_tslab, VR_TSLAB_TU), dim3(1), dim3(64), 0, st);
-    return hipGetLastError();
-}
-#endif
-#if VR_TSLAB_TU == 0
-hipError_t launch_warm_tslab_tu1(hipStream_t st);
-hipError_t launch_warm_tslab_tu2(hipStream_t st);
-hipError_t launch_warm_tslab_tu3(hipStream_t st);
-hipError_t launch_warm_tslab_tu4(hipStream_t st);
-hipError_t launch_warm_tslab_tu5(hipStream_t st);
-hipError_t launch_warm_tslab_tu6(hipStream_t st);
-hipError_t launch_warm_tslab_tu7(hipStream_t st);
-hipError_t launch_warm_tslab_tu8(hipStream_t st);
-hipError_t launch_warm_tslab_tu9(hipStream_t st);
-hipError_t launch_warm_tslab(hipStream_t st)
-{
-    hipError_t e = launch_warm_tslab_tu0(st);
-    if (e == hipSuccess) e = launch_warm_tslab_tu1(st);
-    if (e == hipSuccess) e = launch_warm_tslab_tu2(st);
-    if (e == hipSuccess) e = launch_warm_tslab_tu3(st);
-    if (e == hipSuccess) e = launch_warm_tslab_tu4(st);
-    if (e == hipSuccess) e = launch_warm_tslab_tu5(st);
-    if (e == hipSuccess) e = launch_warm_tslab_tu6(st);
-    if (e == hipSuccess) e = launch_warm_tslab_tu7(st);
-    if (e == hipSuccess) e = launch_warm_tslab_tu8(st);
-    if (e == hipSuccess) e = launch_warm_tslab_tu9(st);
-    return e;
-}
-#elif VR_TSLAB_TU == -1
-hipError_t launch_warm_tslab(hipStream_t) { return hipSuccess; }      // single-unit build: nothing to pre-load separately
-#endif
+// every unit is pre-loaded when TRILINEAR is selected (vr_set_filter / vr_load_shader), so neither the first TRILINEAR frame nor
+// the first frame of a shape the measured choice tries pays for it
+VR_CODE_UNIT(tslab, VR_TSLAB_TU, "trilinear", WARM_TRILINEAR)
 
 }  // namespace vr
-
