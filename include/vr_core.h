@@ -554,6 +554,16 @@ int vr_get_ray_stream_builds(vr_handle h, uint64_t *builds);
    vr_get_ray_stream_bytes is the real allocation either way.  Other mode values: VR_E_INVALID. */
 int vr_set_ray_stream_pack(vr_handle h, int mode);
 int vr_get_ray_stream_pack(vr_handle h, int *mode);
+/* How a replayed frame classifies the grey ramp: arithmetically, or through a table of the window's entries in the CU's local
+   memory whose reads are issued ahead of their use (for a fixed share of the samples: all of them, as built).  The table's
+   entries are computed by the arithmetic path's own operations, so frames are the same bits.  Eligible: grey composite
+   without a transfer function and plain MIP, a window of at most 4096 entries, and -- packed stream -- a window below 2^24 in
+   magnitude.  mode 0: never; 1 (default): where eligible on a packed stream (vr_set_ray_stream_pack) whose samples take
+   more than 256 MiB; 2: wherever eligible.  The stream is not rebuilt and
+   vr_get_last_kernel_name is unchanged.  *used (may be null): 1 if the last replayed frame took the hybrid.  Other mode
+   values: VR_E_INVALID. */
+int vr_set_ray_stream_table(vr_handle h, int mode);
+int vr_get_ray_stream_table(vr_handle h, int *mode, int *used);
 /* 1-D transfer function (N3): n knots of (iso in 0..255, r,g,b,a); n = 0 restores the
    reference grey ramp.  Built with the natural cubic spline of src/CubicSpline.cpp. */
 int vr_set_transfer_function(vr_handle h, const int32_t *iso, const float *rgba4, int n);

@@ -11,6 +11,8 @@ sphere, 1280x720, alpha 1) and the cfg2 shape (512x512x452 u16, 1920x1080, windo
   stream_bytes  vr_get_ray_stream_bytes; padding = the stream's sample bytes / (samples of the frame x bytes per voxel)
   floor_ms      stream_bytes / the vr_measure_stream_read rate of the same process
   bit_identical the replayed frame equals the gathered one, view(uint32)
+  by_table_mode vr_set_ray_stream_table 0, 1 and 2 (never / automatic / wherever eligible) on the same stream: replay_ms, whether
+                the hybrid classification was the path taken, and the frame against the gathered one; replay_ms above is mode 1's
 16-bit shapes also, under `packed` (vr_set_ray_stream_pack 2: raymarch_stream12_kernel, 12 bits per sample): replay_ms, build_ms (a
 build into the kept, larger allocation), stream_bytes (of a fresh handle's allocation: the model's packed size), floor_ms, x_floor,
 bit_identical, and automatic_packs -- whether the default mode packs this shape.
@@ -46,6 +48,17 @@ def kernel_ms(r, n):
     return r.kernelMsTake() / n
 
 
+def table_modes(r, reps, gathered):
+    """the replayed frame under every table mode; leaves the default mode set"""
+    res = {}
+    for m in (0, 1, 2):
+        r.setRayStreamTable(m)
+        res[str(m)] = {"replay_ms": round(kernel_ms(r, reps), 4), "hybrid": r.rayStreamTableUsed(),
+                       "bit_identical": bool(np.array_equal(r.readPixels().view(np.uint32), gathered.view(np.uint32)))}
+    r.setRayStreamTable(1)
+    return res
+
+
 def wall_ms(r):
     r.synchronize()
     t0 = time.perf_counter()
@@ -75,6 +88,7 @@ def measure(vra, name, s, reps):
         out["replay_ms"] = round(kernel_ms(r, reps), 4)
         out["replay_kernel"] = r.last_kernel_name
         out["bit_identical"] = bool(np.array_equal(r.readPixels().view(np.uint32), gathered.view(np.uint32)))
+        out["by_table_mode"] = table_modes(r, reps, gathered)
         out["stream_bytes"] = r.rayStreamBytes()
         out["copies_bytes_before"] = copies
         out["copies_bytes_with_stream"] = r.residentBytes()[1]
@@ -101,6 +115,7 @@ def measure(vra, name, s, reps):
             replay_wall = min(wall_ms(r) for _ in range(5))
             pk = {"build_ms": round(built - replay_wall, 3), "replay_ms": round(kernel_ms(r, reps), 4), "replay_kernel": r.last_kernel_name}
             pk["bit_identical"] = bool(np.array_equal(r.readPixels().view(np.uint32), gathered.view(np.uint32)))
+            pk["by_table_mode"] = table_modes(r, reps, gathered)
             # the packed size from the unpacked one (the allocation on this handle is the kept, larger one): groups of 8 instead
             # of 4 need the blocks' lengths, so it is read from a handle that only ever built the packed stream -- below
             pk["stream_bytes_allocated_here"] = r.rayStreamBytes()

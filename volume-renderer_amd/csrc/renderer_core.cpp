@@ -768,6 +768,12 @@ void RendererCore::setRayStreamPack(int mode)
     copies_.setRayStreamPack(mode);                                      // (another mode: the stream is stale, its allocation is kept)
 }
 
+void RendererCore::setRayStreamTable(int mode)
+{
+    if (mode < 0 || mode > 2) throw std::invalid_argument("setRayStreamTable: unknown mode");
+    ray_stream_table_ = mode;                                            // (the stream holds the same voxels: nothing is rebuilt)
+}
+
 // The ray-ordered sample stream (vr_stream.hip): counts this launch's geometry and decides whether the launch replays.  A launch
 // that cannot replay (another mode or filter, skipping, no tile table) or whose geometry differs from the last one's makes the
 // stream stale at once; its allocation is kept for the next build.  Mode 1: replay from the kRayStreamStillLaunches-th
@@ -1075,7 +1081,16 @@ hipError_t RendererCore::launchKernel(const PreparedLaunch &F, uint32_t *spp)
     }
     case FrameMode::RayMarch: break;
     }
-    if (F.replay && spp == nullptr) return launch_raymarch_stream(P, L, d_tf_.get(), F.fb, copies_.rayStream(), stream(), &last_kernel_);
+    if (F.replay && spp == nullptr) {
+        RayStreamView S = copies_.rayStream();
+        // the hybrid classification: wherever eligible (mode 2), or -- automatic -- on a packed stream larger than the
+        // last-level cache, where it was measured to gain (vr_stream.h: kStreamTableMinBytes)
+        const uint64_t sample_bytes = streamSampleBytes(S.format, L.bytes_per_voxel, copies_.rayStreamElements());
+        const bool automatic = S.format == kStreamPack12 && sample_bytes > kStreamTableMinBytes;
+        S.table = (ray_stream_table_ == 2 || (ray_stream_table_ == 1 && automatic)) ? 1 : 0;
+        last_stream_table_ = S.table != 0 && streamTableEligible(P, L, S);
+        return launch_raymarch_stream(P, L, d_tf_.get(), F.fb, S, stream(), &last_kernel_);
+    }
     return launch_raymarch(P, L, d_vol_.get(), d_tf_.get(), F.fb, spp, stream(), &last_kernel_);
 }
 

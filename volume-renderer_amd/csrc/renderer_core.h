@@ -134,6 +134,12 @@ public:
     // allows.  12 bits per sample instead of 16, the same frames bit for bit; a new mode rebuilds the stream.
     void setRayStreamPack(int mode);
     int rayStreamPack() const { return copies_.rayStreamPack(); }
+    // The hybrid classification of replayed frames (vr_set_ray_stream_table; vr_stream.h: streamTableEligible): 0 never, 1
+    // (default) where eligible on a packed stream whose samples are larger than kStreamTableMinBytes, 2 wherever eligible.  The same
+    // frames bit for bit; the stream is not rebuilt.  rayStreamTableUsed: whether the last replayed frame took it.
+    void setRayStreamTable(int mode);
+    int rayStreamTable() const { return ray_stream_table_; }
+    bool rayStreamTableUsed() const { return last_stream_table_; }
     bool hasDevice() const { return device_ >= 0; }
     void warmTrilinear();                    // pre-load the staged TRILINEAR kernel's code objects (once)
     // first-hit isosurface mode (vr_set_isosurface): while on, frames are the shaded surface and its depth, whatever the MIP /
@@ -326,7 +332,9 @@ private:
         bool replay = false;                 // engageRayStream: this launch reads the stream
     };
     int ray_stream_mode_ = 1;
-    uint64_t volume_generation_ = 0;         // counts the writers of d_vol_ (dropDerived)
+    int ray_stream_table_ = 1;               // vr_set_ray_stream_table
+    bool last_stream_table_ = false;         // the last replayed frame classified a share of its samples through the table
+    uint64_t volume_generation_ = 0;        // counts the writers of d_vol_ (dropDerived)
     bool still_key_valid_ = false;
     RayGeometryKey still_key_;               // the geometry of the last eligible launch ...
     int still_launches_ = 0;                 // ... and how many consecutive launches have had it

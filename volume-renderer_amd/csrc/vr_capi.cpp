@@ -587,6 +587,20 @@ int vr_get_ray_stream_pack(vr_handle h, int *mode)
     });
 }
 
+int vr_set_ray_stream_table(vr_handle h, int mode)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.setRayStreamTable(mode); });
+}
+
+int vr_get_ray_stream_table(vr_handle h, int *mode, int *used)
+{
+    return guarded(h, [&](vr::RendererCore &c) {
+        if (!mode) throw std::invalid_argument("vr_get_ray_stream_table: null result");
+        *mode = c.rayStreamTable();
+        if (used) *used = c.rayStreamTableUsed() ? 1 : 0;
+    });
+}
+
 int vr_get_ray_stream_builds(vr_handle h, uint64_t *builds)
 {
     return guarded(h, [&](vr::RendererCore &c) {

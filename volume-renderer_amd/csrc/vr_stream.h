@@ -31,7 +31,27 @@ struct RayStreamView {
     // three dwords at byte offsets[b] * 3 / 2 + (i / 8) * 768 + l * 12
     StreamFormat format = kStreamRaw;
     int base = 0;
+    int table = 0;                // the frame's choice (RendererCore: vr_set_ray_stream_table): 1 = the hybrid classification where eligible
 };
+
+// The hybrid classification of a replayed frame (vr_stream.hip: TSHARE): a fixed share of the grey ramp's samples through an
+// LDS table of the window's entries.  Eligible: the grey composite without a transfer function and the plain MIP (the other
+// modes classify every sample through their table already), a window of at most kStreamTableMax entries, and -- packed format --
+// a window the stream's base folds into (a window beyond that bound runs the integer add and stays arithmetic).
+constexpr int kStreamTableMax = 4096;         // == FAST_LUT_MAX (vr_device.h)
+// The automatic rule (vr_set_ray_stream_table 1) takes the hybrid on a packed stream whose samples are larger than this (the
+// last-level cache, as the packed format's own rule): the headline's 744 MB gain 10 % and the cfg2 shape's 330 MB 6 %.  Below
+// it, and on the unpacked formats, the gains measured are smaller (3 % on a 122 MB u16 stream, none on 437 MB) and the
+// automatic mode keeps the table-less instances (docs/lab-notebook.md)
+constexpr uint64_t kStreamTableMinBytes = 256ull << 20;
+inline bool streamTableEligible(const FrameParams &P, const LaunchConfig &L, const RayStreamView &S)
+{
+    (void)L;
+    if (P.tf_len > 1 || P.tf_grey != 0) return false;
+    const long long entries = (long long)P.max_val - (long long)P.min_val + 1;
+    if (entries < 1 || entries > kStreamTableMax) return false;
+    return S.format != kStreamPack12 || streamBaseFoldsIntoWindow(P.min_val, P.max_val, S.base);
+}
 
 // pass 1: the geometric sample count n of every ray into counts[blocks * 64] and n_max(block) * 64 -- n_max rounded up to
 // `group` -- into block_elems[blocks]

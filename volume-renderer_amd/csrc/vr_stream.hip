@@ -8,7 +8,8 @@
 // classifies and composites every sample, so window, alpha, transfer-function and MIP changes render from the same stream.
 //
 // The replay loop (raymarch_stream_kernel): a wavefront replays one block and keeps DEPTH loaded groups beyond the DEPTH it
-// composites; the instances without a classification table run as one-wavefront workgroups, eight per tile.
+// composites; the instances without a classification table run as one-wavefront workgroups, eight per tile.  The grey ramp of
+// a large packed stream (vr_set_ray_stream_table) is classified through an LDS table whose reads are asked for a group ahead.
 //
 // Build (once per still view; VolumeCopies::ensureRayStream): stream_record_kernel<COUNT> writes the geometric sample count n
 // of every ray, a device scan turns the blocks' padded lengths into 64-bit element offsets, the host reads the total back --
@@ -53,6 +54,21 @@
 #endif
 static_assert(VR_STREAM_WG == 64 || VR_STREAM_WG == 128 || VR_STREAM_WG == 256 || VR_STREAM_WG == 512,
               "a tile's eight wavefronts are split into 8, 4, 2 or 1 workgroups");
+// The hybrid classification of the grey ramp (vr_set_ray_stream_table; TSHARE of raymarch_stream_kernel): of every four samples
+// VR_STREAM_TSHARE (1, 2 or 4) are classified through the 32 KiB LDS table of (c, a), one ds_read_b64 each, asked for one loaded
+// group ahead, and the rest arithmetically; VR_STREAM_TWG threads per workgroup share one table (512: one per tile, 256: two
+// workgroups per tile, four of which fit a CU's LDS).  Measured: every share at both sizes, and a 16 KiB table of s alone, in
+// docs/lab-notebook.md, "Ray stream: a share of the samples classified through LDS" -- all four through the table, from
+// 256-thread workgroups, is what the headline's stream, the shard's and the 8-bit shape's replay fastest from; no share gains
+// on the unpacked cfg2 stream
+#ifndef VR_STREAM_TSHARE
+#define VR_STREAM_TSHARE 4
+#endif
+#ifndef VR_STREAM_TWG
+#define VR_STREAM_TWG 256
+#endif
+static_assert(VR_STREAM_TSHARE == 1 || VR_STREAM_TSHARE == 2 || VR_STREAM_TSHARE == 4, "table samples per four");
+static_assert(VR_STREAM_TWG == 256 || VR_STREAM_TWG == 512, "a table is shared by four or eight wavefronts of a tile");
 
 namespace vr {
 
@@ -258,9 +274,10 @@ static hipError_t launch_record_type(const FrameParams &P, const LaunchConfig &L
 //  - arithmetic path: the window is shifted, fmin - base and fmax - base (vr_stream_pack.h: streamBaseFoldsIntoWindow has the
 //    reasoning and the bound); BASEADD, for a window beyond that bound: t + base as an integer before the convert.
 typedef uint32_t stream_u32x2 __attribute__((ext_vector_type(2)));
+typedef float stream_f32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t stream_u32x3 __attribute__((ext_vector_type(3)));   // (a register value only: never loaded through a pointer of this type)
 
-template <typename VoxelT, int MODE, bool LUT, bool NOCLAMP, bool PACK = false, bool BASEADD = false>
+template <typename VoxelT, int MODE, bool LUT, bool NOCLAMP, bool PACK = false, bool BASEADD = false, int TSHARE = 0>
 __global__ __launch_bounds__(512) void raymarch_stream_kernel(const FrameParams P, const float4 *__restrict__ tf, float4 *__restrict__ fb,
                                                               const VoxelT *__restrict__ samples, const uint16_t *__restrict__ counts,
                                                               const uint64_t *__restrict__ offsets, const unsigned blocks_x,
@@ -270,10 +287,14 @@ __global__ __launch_bounds__(512) void raymarch_stream_kernel(const FrameParams 
     static_assert(!NOCLAMP || (!LUT && MODE == 0), "the no-clamp specialisation exists for the grey composite's arithmetic classification");
     static_assert(!PACK || sizeof(VoxelT) == 2, "the packed format holds 16-bit voxels");
     static_assert(!BASEADD || (PACK && !LUT), "the integer add replaces the shifted window of the arithmetic path");
+    static_assert(TSHARE == 0 || (!LUT && MODE < 2 && !BASEADD), "the hybrid splits the grey ramp's samples between the table and the shifted window's arithmetic");
+    static_assert(TSHARE == 0 || TSHARE == 1 || TSHARE == 2 || TSHARE == 4, "table samples per four");
     constexpr unsigned G = PACK ? STREAM12_G : STREAM_G, BLOCK_ELEMS = 64u * G;
-    __shared__ float lut[LUT ? FAST_LUT_MAX * 2 : 4];       // 32 KiB: 4096 x (c,a) or 256 x (r,g,b,a) + index bytes
-    // (a table-less instance uses no LDS and no barrier: its tile may be launched as 8 / WPB workgroups of WPB wavefronts)
-    constexpr unsigned WPB = LUT ? 8u : (unsigned)VR_STREAM_WG / 64u, SPLIT = 8u / WPB;
+    constexpr bool TABLE = LUT || TSHARE > 0;                // the instance builds the LDS table
+    __shared__ float lut[TABLE ? FAST_LUT_MAX * 2 : 4];     // 32 KiB: 4096 x (c,a) or 256 x (r,g,b,a) + index bytes
+    // (a table-less instance uses no LDS and no barrier: its tile may be launched as 8 / WPB workgroups of WPB wavefronts; a
+    // hybrid instance's VR_STREAM_TWG threads build and share one table)
+    constexpr unsigned WPB = LUT ? 8u : (TSHARE > 0 ? (unsigned)VR_STREAM_TWG : (unsigned)VR_STREAM_WG) / 64u, SPLIT = 8u / WPB;
     const uint32_t t = tile_table[blockIdx.x / SPLIT];
     if (t == 0xffffffffu) return;                            // padding block
     const unsigned tx = t & 0xffffu, ty = t >> 16;
@@ -295,12 +316,12 @@ __global__ __launch_bounds__(512) void raymarch_stream_kernel(const FrameParams 
     const uint64_t off = offsets[sb];
     const uint32_t ngroups = (uint32_t)((offsets[sb + 1] - off) / BLOCK_ELEMS);
 
-    if (LUT) {
+    if (TABLE) {
         // the classification table, exactly as raymarch_fast_kernel builds it (vr_fast.hip:100-144); tabulated only if some ray
         // of the workgroup has a sample
         if (__syncthreads_or(n > 0 ? 1 : 0)) {
             const int ne = P.max_val - P.min_val + 1;
-            for (int e = (int)threadIdx.x; e < ne; e += 512) {
+            for (int e = (int)threadIdx.x; e < ne; e += (int)(WPB * 64u)) {
                 const float s = (float)(P.min_val + e);          // == clamp(float(texel), fmin, fmax)
                 const float v = div_cert(s - P.fmin, P.fden, P.rden);
                 if (MODE >= 2) {
@@ -372,6 +393,18 @@ __global__ __launch_bounds__(512) void raymarch_stream_kernel(const FrameParams 
                 c = s * a;
             }
         };
+        // the hybrid's table sample: the entry of clamp(texel) -- the (c, a) the arithmetic above gives, computed by the same
+        // operations when the table was built.  Only the read is issued here: the loop below asks for a group's entries one
+        // group ahead of their use
+        auto table_read = [&](uint32_t texel) -> stream_f32x2 {
+            int v = (int)texel;
+            if (!NOCLAMP) v = med3_i32(v, cmin, cmax);
+            uint32_t entry;
+            asm("v_lshl_add_u32 %0, %1, 3, %2" : "=v"(entry) : "v"(v), "v"(lut_entry0));
+            return *reinterpret_cast<VR_LDS_AS const stream_f32x2 *>((size_t)entry);     // (one ds_read_b64: an entry is 8-byte aligned)
+        };
+        // which of a group's four samples go through the table: the same positions in every lane
+        auto table_pos = [](int u) { return TSHARE == 4 || (TSHARE == 2 && (u & 1) != 0) || (TSHARE == 1 && u == 3); };
         // one sample onto the destination: front-to-back composite (VolumeRenderer.cs:132-133) or MIP's running maximum
         // (:165-168) -- accumulate of vr_fast.hip:334-345
         auto accumulate = [&](float c, float cg, float cb, float a) {
@@ -417,11 +450,22 @@ __global__ __launch_bounds__(512) void raymarch_stream_kernel(const FrameParams 
         // (VolumeRenderer.cs:118) passed for the whole group; the group in which a ray ends -- by that test or at its own n --
         // runs the literal per-sample tests, and its padded slots are never composited.  u0: the first of the four inside the
         // load's group (PACK: a group of 8 is consumed as two groups of four, u0 = 0 and 4)
-        auto consume = [&](const GroupT &w, int i0, int u0) {
+        // te (TSHARE): the table entries of the four, read ahead (table_read), valid at the table positions
+        auto consume = [&](const GroupT &w, int i0, int u0, const stream_f32x2 *te) {
             if (!alive) return;
             float c[STREAM_G], cg[STREAM_G], cb[STREAM_G], a[STREAM_G];
+            if constexpr (TSHARE > 0) {
+                // the arithmetic samples first: they cover what is left of the table reads' latency
 #pragma unroll
-            for (int u = 0; u < (int)STREAM_G; u++) { cg[u] = 0.0f; cb[u] = 0.0f; classify(texel_of(w, u0 + u), c[u], cg[u], cb[u], a[u]); }
+                for (int u = 0; u < (int)STREAM_G; u++) { cg[u] = 0.0f; cb[u] = 0.0f; if (!table_pos(u)) classify(texel_of(w, u0 + u), c[u], cg[u], cb[u], a[u]); }
+#pragma unroll
+                for (int u = 0; u < (int)STREAM_G; u++) {
+                    if (table_pos(u)) { c[u] = te[u].x; a[u] = te[u].y; }
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < (int)STREAM_G; u++) { cg[u] = 0.0f; cb[u] = 0.0f; classify(texel_of(w, u0 + u), c[u], cg[u], cb[u], a[u]); }
+            }
             const float drgb0 = drgb, dg0 = dg, db0 = db, da0 = da;
             float da_last = 0.0f;
 #pragma unroll
@@ -444,10 +488,28 @@ __global__ __launch_bounds__(512) void raymarch_stream_kernel(const FrameParams 
         for (uint32_t g0 = 0; g0 < ngroups; g0 += (uint32_t)K) {
 #pragma unroll
             for (int k = 0; k < K; k++) nxt[k] = load_group(g0 + (uint32_t)(K + k));
+            if constexpr (TSHARE > 0) {
+                // a loaded group's table entries are asked for while the group before it is composited, by every lane (a lane
+                // that has ended reads entries of its own slots: values of the volume, or the padding's), and waited for in
+                // the order they were asked
+                stream_f32x2 te[2][G];
+                auto table_group = [&](const GroupT &w, stream_f32x2 *e) {
 #pragma unroll
-            for (int k = 0; k < K; k++) {
-                consume(cur[k], (int)((g0 + (uint32_t)k) * G), 0);
-                if (PACK) consume(cur[k], (int)((g0 + (uint32_t)k) * G + STREAM_G), (int)STREAM_G);
+                    for (int u = 0; u < (int)G; u++) if (table_pos(u % (int)STREAM_G)) e[u] = table_read(texel_of(w, u));
+                };
+                table_group(cur[0], te[0]);
+#pragma unroll
+                for (int k = 0; k < K; k++) {
+                    if (k + 1 < K) table_group(cur[k + 1], te[(k + 1) & 1]);
+                    consume(cur[k], (int)((g0 + (uint32_t)k) * G), 0, te[k & 1]);
+                    if (PACK) consume(cur[k], (int)((g0 + (uint32_t)k) * G + STREAM_G), (int)STREAM_G, te[k & 1] + STREAM_G);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < K; k++) {
+                    consume(cur[k], (int)((g0 + (uint32_t)k) * G), 0, nullptr);
+                    if (PACK) consume(cur[k], (int)((g0 + (uint32_t)k) * G + STREAM_G), (int)STREAM_G, nullptr);
+                }
             }
 #pragma unroll
             for (int k = 0; k < K; k++) cur[k] = nxt[k];
@@ -470,11 +532,19 @@ static hipError_t launch_replay_mode(const FrameParams &P, const LaunchConfig &L
     constexpr unsigned SPLIT = 512u / (unsigned)VR_STREAM_WG;
     if (L.tile_table_blocks > 0x7fffffffu / SPLIT) return hipErrorInvalidValue;
     const dim3 grid_nolut(L.tile_table_blocks * SPLIT), block_nolut((unsigned)VR_STREAM_WG);
-    // The grey ramp is classified ARITHMETICALLY here, whatever the window: the table look-up (one ds_read_b64 per sample at a
-    // data-dependent address, what the gather kernels use) is what this kernel would wait for -- cfg3 0.246 ms with it, 0.226
-    // without (docs/lab-notebook.md) -- and the table's entries are these same operations, so the bits are the same.  Tables
-    // remain for the transfer function (MODE >= 2) and its grey fold.
+    // Without S.table the grey ramp is classified ARITHMETICALLY, whatever the window: a table look-up asked for when the sample
+    // is composited (one read per sample at a data-dependent address, what the gather kernels and the LUT instances do) is
+    // what this kernel would wait for -- cfg3 0.246 ms with it, 0.226 without (docs/lab-notebook.md) -- and the table's
+    // entries are these same operations, so the bits are the same.  Tables remain for the transfer function (MODE >= 2) and
+    // its grey fold.
     const bool lut = MODE >= 2 ? L.use_lut != 0 : P.tf_grey != 0;
+    // The hybrid (S.table; streamTableEligible): VR_STREAM_TSHARE of every four samples through the table, every read asked for
+    // one loaded group ahead of its use, in workgroups of VR_STREAM_TWG threads that share one table.  The table samples' bits
+    // are the arithmetic samples' (the entries are those operations), so the choice never shows in a frame.
+    static_assert(kStreamTableMax == FAST_LUT_MAX, "vr_stream.h: kStreamTableMax");
+    const bool hybrid = MODE < 2 && S.table != 0 && streamTableEligible(P, L, S);
+    constexpr unsigned TSPLIT = 512u / (unsigned)VR_STREAM_TWG;
+    const dim3 grid_t(L.tile_table_blocks * TSPLIT), block_t((unsigned)VR_STREAM_TWG);
     if constexpr (PACK) {
         // the stream's own base travels in the frame's parameters (pk12_base is otherwise the packed volume copy's, which the
         // replay never reads); a window the shifted constants cannot hold exactly takes the integer add (BASEADD)
@@ -484,32 +554,47 @@ static hipError_t launch_replay_mode(const FrameParams &P, const LaunchConfig &L
 #define VR_REPLAY12(LT, NC, BA)                                                                                                   \
     hipLaunchKernelGGL((raymarch_stream_kernel<VoxelT, MODE, LT, NC, true, BA>), LT ? grid : grid_nolut, LT ? block : block_nolut, 0, st, Q, tf, fb, \
                        (const VoxelT *)S.samples, S.counts, S.offsets, g.blocks_x, L.tile_table)
+#define VR_REPLAY12_T1(TS) hipLaunchKernelGGL((raymarch_stream_kernel<VoxelT, MODE, false, true, true, false, TS>), grid_t, block_t, 0, st, Q, tf, fb, \
+                                              (const VoxelT *)S.samples, S.counts, S.offsets, g.blocks_x, L.tile_table)
+#define VR_REPLAY12_T0(TS) hipLaunchKernelGGL((raymarch_stream_kernel<VoxelT, MODE, false, false, true, false, TS>), grid_t, block_t, 0, st, Q, tf, fb, \
+                                              (const VoxelT *)S.samples, S.counts, S.offsets, g.blocks_x, L.tile_table)
         if constexpr (MODE == 0) {
             if (lut) VR_REPLAY12(true, false, false);
+            else if (hybrid) { if (L.lut_noclamp != 0) VR_REPLAY12_T1(VR_STREAM_TSHARE); else VR_REPLAY12_T0(VR_STREAM_TSHARE); }
             else if (L.lut_noclamp != 0) { if (shift) VR_REPLAY12(false, true, false); else VR_REPLAY12(false, true, true); }
             else { if (shift) VR_REPLAY12(false, false, false); else VR_REPLAY12(false, false, true); }
         } else if constexpr (MODE == 1) {
-            if (shift) VR_REPLAY12(false, false, false); else VR_REPLAY12(false, false, true);
+            if (hybrid) VR_REPLAY12_T0(VR_STREAM_TSHARE);
+            else if (shift) VR_REPLAY12(false, false, false); else VR_REPLAY12(false, false, true);
         } else {
             if (!lut) return hipErrorInvalidValue;
             VR_REPLAY12(true, false, false);
         }
+#undef VR_REPLAY12_T0
+#undef VR_REPLAY12_T1
 #undef VR_REPLAY12
         return hipGetLastError();
     } else {
 #define VR_REPLAY(LT, NC)                                                                                                        \
     hipLaunchKernelGGL((raymarch_stream_kernel<VoxelT, MODE, LT, NC>), LT ? grid : grid_nolut, LT ? block : block_nolut, 0, st, P, tf, fb, (const VoxelT *)S.samples, \
                        S.counts, S.offsets, g.blocks_x, L.tile_table)
+#define VR_REPLAY_T1(TS) hipLaunchKernelGGL((raymarch_stream_kernel<VoxelT, MODE, false, true, false, false, TS>), grid_t, block_t, 0, st, P, tf, fb, \
+                                            (const VoxelT *)S.samples, S.counts, S.offsets, g.blocks_x, L.tile_table)
+#define VR_REPLAY_T0(TS) hipLaunchKernelGGL((raymarch_stream_kernel<VoxelT, MODE, false, false, false, false, TS>), grid_t, block_t, 0, st, P, tf, fb, \
+                                            (const VoxelT *)S.samples, S.counts, S.offsets, g.blocks_x, L.tile_table)
     if constexpr (MODE == 0) {
         if (lut) VR_REPLAY(true, false);
+        else if (hybrid) { if (L.lut_noclamp != 0) VR_REPLAY_T1(VR_STREAM_TSHARE); else VR_REPLAY_T0(VR_STREAM_TSHARE); }
         else if (L.lut_noclamp != 0) VR_REPLAY(false, true);            // the data's exact range lies inside the window: clamp() is the identity
         else VR_REPLAY(false, false);
     } else if constexpr (MODE == 1) {
-        VR_REPLAY(false, false);
+        if (hybrid) VR_REPLAY_T0(VR_STREAM_TSHARE); else VR_REPLAY(false, false);
     } else {
         if (!lut) return hipErrorInvalidValue;               // (fast_path_eligible: a transfer function needs the table)
         VR_REPLAY(true, false);
     }
+#undef VR_REPLAY_T0
+#undef VR_REPLAY_T1
 #undef VR_REPLAY
     return hipGetLastError();
     }

@@ -163,6 +163,8 @@ def load_library() -> C.CDLL:
         "vr_get_ray_stream_builds": (i32, [h, C.POINTER(C.c_uint64)]),
         "vr_set_ray_stream_pack": (i32, [h, i32]),
         "vr_get_ray_stream_pack": (i32, [h, C.POINTER(i32)]),
+        "vr_set_ray_stream_table": (i32, [h, i32]),
+        "vr_get_ray_stream_table": (i32, [h, C.POINTER(i32), C.POINTER(i32)]),
         "vr_set_pack12": (i32, [h, i32]),
         "vr_get_pack12_bytes": (i32, [h, C.POINTER(C.c_size_t)]),
         "vr_set_trilinear_copy": (i32, [h, i32]),
@@ -884,6 +886,24 @@ class RendererCore:
         m = C.c_int32()
         self._check(self._lib.vr_get_ray_stream_pack(self._h, C.byref(m)))
         return m.value
+
+    RAY_STREAM_TABLE_OFF, RAY_STREAM_TABLE_AUTO, RAY_STREAM_TABLE_ALWAYS = 0, 1, 2
+
+    def setRayStreamTable(self, mode):
+        """the hybrid classification of replayed grey-ramp frames (a share of the samples through an LDS table): 0 never, 1
+        automatic (default: packed streams of more than 256 MiB), 2 wherever eligible"""
+        self._check(self._lib.vr_set_ray_stream_table(self._h, int(mode)))
+
+    def rayStreamTable(self) -> int:
+        m = C.c_int32()
+        self._check(self._lib.vr_get_ray_stream_table(self._h, C.byref(m), None))
+        return m.value
+
+    def rayStreamTableUsed(self) -> bool:
+        """whether the last replayed frame took the hybrid classification"""
+        m, u = C.c_int32(), C.c_int32()
+        self._check(self._lib.vr_get_ray_stream_table(self._h, C.byref(m), C.byref(u)))
+        return bool(u.value)
 
     def setTrilinearCopy(self, on):
         self._check(self._lib.vr_set_trilinear_copy(self._h, int(bool(on))))
