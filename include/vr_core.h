@@ -454,6 +454,60 @@ int vr_get_components_ms(vr_handle h, float *ms);
 int vr_simplify_mesh(vr_handle h, float cell, uint64_t *n_vertices, uint64_t *n_triangles);
 int vr_get_mesh_simplification(vr_handle h, float *cell, uint64_t *source_vertices, uint64_t *source_triangles);
 int vr_get_simplify_ms(vr_handle h, float *ms);
+/* Smoothing of the resident mesh, computed on the device (no reference equivalent; Taubin's lambda|mu filter, the step VTK's
+   vtkSmoothPolyDataFilter / vtkWindowedSincPolyDataFilter and 3D Slicer's "Smoothing factor" put last): vr_smooth_mesh replaces
+   the positions and normals of the handle's mesh, whichever extraction or simplification made it, by their smoothed values.  The
+   triangles, V and T are unchanged; vr_get_mesh_info, vr_read_mesh, vr_save_mesh and vr_free_mesh serve the result.  Every fp32
+   step is one correctly rounded operation in the order given, nothing contracted:
+   1. Input: the resident mesh, V vertices and T triangles; iterations, lambda, mu, fix_boundary.
+   2. Graph: every triangle (a, b, c) contributes the directed pairs (a,b), (b,a), (b,c), (c,b), (c,a), (a,c).  Pairs with equal
+      ends are ignored (no extraction or simplification produces them; the definition is total).  N(i) is the set of distinct j
+      with a pair (i, j), k_i = |N(i)|.  The multiplicity of {i, j} is the number of pairs (i, j): the number of triangles that
+      contain the edge.  The graph is built on indices, not positions: coincident vertices, which the extraction produces where
+      s_A == iso_s, are different vertices.
+   3. Fixed vertices: with fix_boundary != 0 a vertex is FIXED when it is an end of an edge of multiplicity exactly 1; with
+      fix_boundary == 0 nothing is fixed.  A vertex with k_i = 0 never moves.  On an extracted mesh the fixed vertices are
+      exactly those where the open surface meets the volume's boundary, so the cut stays planar; on a simplified mesh they are
+      also the ends of edges that clustering left with one triangle.
+   4. A step with factor phi is Jacobi: every vertex reads the positions from before the step.  For every vertex i that is not
+      fixed and has k_i > 0, per axis a: acc = 0.0f; acc = acc + p_j,a over j in N(i) in ascending j; m = acc / (float)k_i (one
+      division); d = m - p_i,a; p'_i,a = p_i,a + phi * d (the product, then the sum).  All other vertices keep their bits.
+   5. An iteration: a step with phi = lambda, then a step with phi = mu; the mu step is skipped when mu == 0 (plain Laplacian
+      smoothing).  `iterations` iterations are run.
+   6. Normals: recomputed from the result (the stored gradient normals belong to the old positions).  Per triangle t with corners
+      p0, p1, p2: u = p1 - p0, w = p2 - p0, c_x = u_y*w_z - u_z*w_y and c_y, c_z cyclically (each two products and one
+      subtraction).  Per vertex: S = (0, 0, 0); S_a = S_a + c(t)_a over every (t, corner) that references the vertex, in ascending
+      (t, corner); dot = (S_z*S_z + S_y*S_y) + S_x*S_x; N = S * (1.0f / sqrtf(dot)), and (0, 0, 0) when dot == 0 -- the
+      extraction's step 5 normalisation.  The front face is counter-clockwise seen from outside, so N points the way the old
+      normals did.  A vertex no triangle references gets (0, 0, 0).
+   7. iterations == 0: VR_OK, the mesh keeps every byte including its normals, nothing is launched.
+   8. Consequences: smoothing n then m iterations with the same lambda, mu and flag gives the bytes of n + m iterations (the mesh
+      is a product: unlike vr_smooth_volume, which always starts from the volume as loaded, calls accumulate); the triangles are
+      untouched; fixed vertices keep their position bits.  A mu < 0 step can push a coordinate below 0 near the origin, and
+      vr_simplify_mesh refuses such a mesh by its own step 2: the order is simplify, then smooth.
+   9. Parameters and errors, checked in this order: a host-only handle: VR_E_NO_DEVICE; iterations outside [0, 1000], lambda not
+      finite or not in (0, 1], mu not finite or not in [-2, 0]: VR_E_INVALID; no mesh: VR_E_INVALID; 6*T > 2^32 - 1 (pair numbers
+      and row offsets are 32-bit): VR_E_INVALID and a message for vr_take_message; a device allocation that fails: VR_E_NOMEM.
+      The new arrays are swapped in at the very end: after any error the previous mesh is still there.  No rendering state
+      changes (window, modes, copies, launch choices, stream), the labelling is kept and success queues no message.  The empty
+      mesh smooths to the empty mesh.
+   10. vr_get_mesh_smoothing (any pointer may be NULL): the arguments of the last successful vr_smooth_mesh on this mesh and its
+      number of fixed vertices (0 where that call launched nothing: iterations == 0 or the empty mesh); iterations 0 and the rest
+      0 after any extraction or simplification -- a new mesh is unsmoothed; before the first mesh and after vr_free_mesh:
+      VR_E_INVALID.  vr_get_mesh_simplification and vr_get_mesh_info are unaffected.
+   11. vr_get_mesh_smooth_ms: measurement aid: HIP-event times, in ms, of the last successful vr_smooth_mesh, split into building
+      the graph (pairs, sort, rows, fixed vertices) and everything after it (steps and normals); allocations, read-backs and
+      host work excluded; 0 before the first call and after one that launched nothing.  Either pointer may be NULL, both:
+      VR_E_INVALID.
+   Memory: work arrays live on the device and are freed before the call returns.  While the graph is built 120 bytes a triangle
+   (the six 64-bit pairs before and after their sort, their run heads) plus 12 bytes a vertex (rows, fixed flags) plus 4 bytes
+   a distinct pair (3 T on a closed manifold, at most 6 T); during the steps 32 bytes a vertex (rows, two more copies of the
+   positions) plus the neighbours; for the normals 16 bytes a triangle of face vectors and 48 of corners before and after
+   their sort, and 32 bytes a vertex (the corner rows, the new positions and normals); rocPRIM's sort scratch on top, at most
+   one more copy of what is being sorted.  VR_E_NOMEM where that does not fit. */
+int vr_smooth_mesh(vr_handle h, int iterations, float lambda, float mu, int fix_boundary);
+int vr_get_mesh_smoothing(vr_handle h, int *iterations, float *lambda, float *mu, int *fix_boundary, uint64_t *fixed_vertices);
+int vr_get_mesh_smooth_ms(vr_handle h, float *build_ms, float *iterate_ms);
 /* kernel selection: 0 = automatic (specialised kernels when the configuration allows; launches far from filling the
    chip -- fewer than 256 active 32x16 tiles, 1024 when the view is oblique to the volume axes -- use the 4-wavefront
    relay kernel; the fast kernel runs its software-pipelined batch loop unless alpha_scale >= 0.5),

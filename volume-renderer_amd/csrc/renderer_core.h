@@ -191,6 +191,18 @@ public:
     // the cell of the simplification that made the resident mesh (0: an extraction did) and the counts of the mesh it was given
     void meshSimplification(float *cell, uint64_t *source_vertices, uint64_t *source_triangles) const;
     float lastSimplifyMs() const { return last_simplify_ms_; }   // HIP-event time of the last simplification's kernels and device sorts
+    // smoothing of the resident mesh (vr_smooth_mesh; vr_meshsmooth.hip): `iterations` times a Jacobi step
+    // towards the mean of the distinct neighbours with factor lambda, then one with factor mu (skipped when mu == 0); the normals
+    // are recomputed from the result; the triangles stay.  With fix_boundary the ends of edges with one triangle do not move.
+    // iterations outside [0, 1000], lambda outside (0, 1], mu outside [-2, 0], no mesh: std::invalid_argument; 6 T > 2^32 - 1: a
+    // queued message and std::invalid_argument; an allocation that fails: DeviceMemoryError; in each case the previous mesh stays.
+    // Calls accumulate: n then m iterations are n + m.  No rendering state changes and the labelling is kept.
+    void smoothMesh(int iterations, float lambda, float mu, int fix_boundary);
+    // the arguments of the last successful smoothMesh on the resident mesh and its number of fixed vertices; all 0 on a new mesh
+    void meshSmoothing(int *iterations, float *lambda, float *mu, int *fix_boundary, uint64_t *fixed_vertices) const;
+    // HIP-event times of the last successful smoothMesh: building the graph, and the steps and normals (0: nothing was launched)
+    float lastMeshSmoothBuildMs() const { return last_mesh_smooth_build_ms_; }
+    float lastMeshSmoothIterateMs() const { return last_mesh_smooth_iterate_ms_; }
     // connected components of the inside voxels (s >= iso) of the volume being rendered under the 14-neighbourhood of the
     // extraction's edge directions (vr_label_components; vr_components.hip).  The labels stay on the device
     // (4 bytes a voxel, under `other`), the records come to the host, where the selection is made.  Unlike the mesh the labelling
@@ -250,6 +262,12 @@ private:
     float mesh_cell_ = 0.0f;                 // meshSimplification
     uint64_t mesh_src_nv_ = 0, mesh_src_nt_ = 0;
     float last_simplify_ms_ = 0.0f;
+    int mesh_smooth_iterations_ = 0;         // meshSmoothing
+    float mesh_smooth_lambda_ = 0.0f, mesh_smooth_mu_ = 0.0f;
+    bool mesh_smooth_fix_ = false;
+    uint64_t mesh_smooth_fixed_ = 0;
+    float last_mesh_smooth_build_ms_ = 0.0f, last_mesh_smooth_iterate_ms_ = 0.0f;
+    void clearMeshSmoothing();
     uint64_t meshBytes() const;              // device bytes of the mesh
     // the shared body of extractIsosurface and extractComponents; selected: launch_components_plane's bits or nullptr; ms: kernel time so far
     void extractMesh(int32_t iso, float iso_s, const uint64_t *selected, float ms, uint64_t *n_vertices, uint64_t *n_triangles);

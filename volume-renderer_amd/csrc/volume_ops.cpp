@@ -1,7 +1,7 @@
 // volume_ops.cpp -- RendererCore members that compute on the resident volume outside a frame: Gaussian smoothing
 // (vr_smooth_volume), isosurface extraction with its mesh (vr_extract_isosurface; section 1.5) and the
-// connected components with the filtered extraction (vr_label_components, vr_extract_components; section 1.6), and the mesh's
-// simplification by vertex clustering (vr_simplify_mesh; section 1.7).
+// connected components with the filtered extraction (vr_label_components, vr_extract_components; section 1.6), the mesh's
+// simplification by vertex clustering (vr_simplify_mesh; section 1.7) and its smoothing (vr_smooth_mesh; section 1.8).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -10,6 +10,7 @@
 #include "renderer_core.h"
 #include "vr_components.h"
 #include "vr_mesh.h"
+#include "vr_meshsmooth.h"
 #include "vr_simplify.h"
 #include "vr_smooth.h"
 
@@ -138,6 +139,7 @@ void RendererCore::freeMesh()
     d_mesh_pos_.reset(); d_mesh_nrm_.reset(); d_mesh_tri_.reset();
     mesh_nv_ = mesh_nt_ = 0;
     mesh_valid_ = false;
+    clearMeshSmoothing();                                // (a new mesh is unsmoothed)
 }
 
 // Two passes over the z slabs the workspace allows.  The first counts and scans every slab and keeps only the slabs' totals: the
@@ -371,6 +373,131 @@ void RendererCore::meshSimplification(float *cell, uint64_t *source_vertices, ui
     if (cell) *cell = mesh_cell_;
     if (source_vertices) *source_vertices = mesh_src_nv_;
     if (source_triangles) *source_triangles = mesh_src_nt_;
+}
+
+// ---------------------------------------------------------------- mesh smoothing (vr_smooth_mesh)
+// Two timed stretches.  The graph: pairs, their sort, the run heads and their sums, a read-back of the number of distinct pairs
+// (it sizes the neighbour array), the rows, the fixed vertices.  Then everything after it: the 2 * iterations steps -- the first
+// reads the mesh's positions, the others go between two new buffers -- the face vectors, the sort of the corners, the normals.  The arrays of a stretch are
+// freed as soon as nothing reads them; the new positions and normals are swapped in at the very end, the triangles stay.
+void RendererCore::smoothMesh(int iterations, float lambda, float mu, int fix_boundary)
+{
+    requireDevice("smoothMesh");
+    if (iterations < 0 || iterations > 1000) throw std::invalid_argument("smoothMesh: iterations must be in [0, 1000]");
+    if (!std::isfinite(lambda) || !(lambda > 0.0f && lambda <= 1.0f)) throw std::invalid_argument("smoothMesh: lambda must be in (0, 1]");
+    if (!std::isfinite(mu) || !(mu >= -2.0f && mu <= 0.0f)) throw std::invalid_argument("smoothMesh: mu must be in [-2, 0]");
+    if (!mesh_valid_) throw std::invalid_argument("smoothMesh: no isosurface has been extracted");
+    const uint64_t nv = mesh_nv_, nt = mesh_nt_;
+    if (nt > kMeshSmoothMaxPairs / 6) {
+        setMessage("Error!", "The mesh has " + std::to_string(nt) + " triangles: six times that is more than the 32-bit pair numbers of the smoothing "
+                                 "address. Simplify the mesh first.");
+        throw std::invalid_argument("smoothMesh: more than 2^32 - 1 directed pairs");
+    }
+    float build_ms = 0.0f, iterate_ms = 0.0f;
+    uint32_t n_fixed = 0;
+    if (iterations > 0 && nv > 0) {
+        auto bitsOf = [](uint64_t m) { uint32_t b = 0; while (m) { b++; m >>= 1; } return b; };
+        const uint32_t vb = bitsOf(nv - 1);
+        const uint64_t np = 6 * nt, nc = 3 * nt;
+        DeviceBuffer<float> pos, nrm;                    // the new arrays
+        DeviceBuffer<uint8_t> temp;
+        auto scratch = [&](size_t bytes) { if (temp.bytes() < bytes || !temp) temp.allocOrNoMemory(bytes ? bytes : 16, "smoothMesh: hipMalloc(sort scratch)"); };
+        // ---- the graph
+        DeviceBuffer<uint32_t> row, neighbour;           // (begin, end) per vertex into the distinct neighbours, ascending within a row
+        row.allocOrNoMemory(2 * nv, "smoothMesh: hipMalloc(rows)");
+        hipError_t e = hipMemsetAsync(row.get(), 0, row.bytes(), stream());
+        if (np > 0) {
+            DeviceBuffer<uint64_t> key, key_sorted;
+            DeviceBuffer<uint32_t> head, fixed, count;
+            key.allocOrNoMemory(np, "smoothMesh: hipMalloc(pairs)");
+            key_sorted.allocOrNoMemory(np, "smoothMesh: hipMalloc(sorted pairs)");
+            head.allocOrNoMemory(np + 1, "smoothMesh: hipMalloc(run heads)");
+            if (fix_boundary) {
+                fixed.allocOrNoMemory(nv, "smoothMesh: hipMalloc(fixed flags)");
+                count.allocOrNoMemory(1, "smoothMesh: hipMalloc(fixed count)");
+            }
+            const uint32_t key_bits = std::max(2 * vb, 1u);
+            scratch(std::max(meshsmooth_sort_keys_temp_bytes(np, key_bits), meshsmooth_scan_temp_bytes(np + 1)));
+            if (e == hipSuccess && fix_boundary) e = hipMemsetAsync(fixed.get(), 0, fixed.bytes(), stream());
+            if (e == hipSuccess && fix_boundary) e = hipMemsetAsync(count.get(), 0, count.bytes(), stream());
+            if (e == hipSuccess) e = hipEventRecord(ev0_, stream());
+            if (e == hipSuccess) e = launch_meshsmooth_pairs(d_mesh_tri_.get(), nt, vb, key.get(), stream());
+            if (e == hipSuccess) e = launch_meshsmooth_sort_keys(temp.get(), temp.bytes(), key.get(), key_sorted.get(), np, key_bits, stream());
+            if (e == hipSuccess) e = launch_meshsmooth_heads(key_sorted.get(), np, vb, head.get(), fix_boundary ? fixed.get() : nullptr, stream());
+            if (e == hipSuccess) e = launch_meshsmooth_scan(head.get(), np + 1, temp.get(), temp.bytes(), stream());
+            check(finishTimed(e, build_ms), "mesh smoothing kernels (pairs)");
+            key.reset();
+            uint32_t distinct = 0;
+            check(hipMemcpy(&distinct, head.get() + np, sizeof(distinct), hipMemcpyDeviceToHost), "hipMemcpy(D2H distinct pairs)");
+            neighbour.allocOrNoMemory(std::max<size_t>(distinct, 1), "smoothMesh: hipMalloc(neighbours)");
+            e = hipEventRecord(ev0_, stream());
+            if (e == hipSuccess) e = launch_meshsmooth_rows(key_sorted.get(), head.get(), np, vb, neighbour.get(), row.get(), stream());
+            if (e == hipSuccess && fix_boundary) e = launch_meshsmooth_fix(fixed.get(), nv, row.get(), count.get(), stream());
+            check(finishTimed(e, build_ms), "mesh smoothing kernels (rows)");
+            if (fix_boundary) check(hipMemcpy(&n_fixed, count.get(), sizeof(n_fixed), hipMemcpyDeviceToHost), "hipMemcpy(D2H fixed count)");
+        } else {
+            neighbour.allocOrNoMemory(1, "smoothMesh: hipMalloc(neighbours)");
+            check(e, "hipMemset(rows)");
+        }
+        // ---- the steps
+        DeviceBuffer<float> other;                       // pos and other take turns as a step's output
+        pos.allocOrNoMemory(3 * nv, "smoothMesh: hipMalloc(positions)");
+        if (iterations > 1 || mu != 0.0f) other.allocOrNoMemory(3 * nv, "smoothMesh: hipMalloc(positions)");
+        const float *from = d_mesh_pos_.get();
+        e = hipEventRecord(ev0_, stream());
+        for (int it = 0; it < iterations && e == hipSuccess; it++)
+            for (int half = 0; half < 2 && e == hipSuccess; half++) {
+                if (half == 1 && mu == 0.0f) continue;  // plain Laplacian smoothing
+                float *const to = from == pos.get() ? other.get() : pos.get();
+                e = launch_meshsmooth_step(from, to, row.get(), neighbour.get(), nv, half ? mu : lambda, stream());
+                from = to;
+            }
+        check(finishTimed(e, iterate_ms), "mesh smoothing kernels (steps)");
+        row.reset(); neighbour.reset();
+        if (from == other.get()) pos.swap(other);       // pos: the result
+        other.reset();
+        // ---- the normals
+        DeviceBuffer<float> face;
+        DeviceBuffer<uint32_t> corner_row, vertex, number, vertex_sorted, number_sorted;
+        face.allocOrNoMemory(std::max<size_t>(4 * nt, 4), "smoothMesh: hipMalloc(face vectors)");
+        corner_row.allocOrNoMemory(2 * nv, "smoothMesh: hipMalloc(corner rows)");
+        number_sorted.allocOrNoMemory(std::max<size_t>(nc, 1), "smoothMesh: hipMalloc(sorted corners)");
+        nrm.allocOrNoMemory(3 * nv, "smoothMesh: hipMalloc(normals)");
+        if (nc > 0) {
+            vertex.allocOrNoMemory(nc, "smoothMesh: hipMalloc(corner vertices)");
+            number.allocOrNoMemory(nc, "smoothMesh: hipMalloc(corners)");
+            vertex_sorted.allocOrNoMemory(nc, "smoothMesh: hipMalloc(sorted corner vertices)");
+            scratch(meshsmooth_sort_pairs_temp_bytes(nc, std::max(vb, 1u)));
+        }
+        e = hipMemsetAsync(corner_row.get(), 0, corner_row.bytes(), stream());
+        if (e == hipSuccess) e = hipEventRecord(ev0_, stream());
+        if (nc > 0) {
+            if (e == hipSuccess) e = launch_meshsmooth_faces(pos.get(), d_mesh_tri_.get(), nt, face.get(), vertex.get(), number.get(), stream());
+            if (e == hipSuccess) e = launch_meshsmooth_sort_pairs(temp.get(), temp.bytes(), vertex.get(), vertex_sorted.get(), number.get(), number_sorted.get(), nc, std::max(vb, 1u), stream());
+            if (e == hipSuccess) e = launch_meshsmooth_corner_rows(vertex_sorted.get(), nc, corner_row.get(), stream());
+        }
+        if (e == hipSuccess) e = launch_meshsmooth_normals(face.get(), corner_row.get(), number_sorted.get(), nv, nrm.get(), stream());
+        check(finishTimed(e, iterate_ms), "mesh smoothing kernels (normals)");
+        d_mesh_pos_ = std::move(pos); d_mesh_nrm_ = std::move(nrm);
+    }
+    mesh_smooth_iterations_ = iterations; mesh_smooth_lambda_ = lambda; mesh_smooth_mu_ = mu; mesh_smooth_fix_ = fix_boundary != 0;
+    mesh_smooth_fixed_ = n_fixed;
+    last_mesh_smooth_build_ms_ = build_ms; last_mesh_smooth_iterate_ms_ = iterate_ms;
+}
+
+void RendererCore::meshSmoothing(int *iterations, float *lambda, float *mu, int *fix_boundary, uint64_t *fixed_vertices) const
+{
+    if (!mesh_valid_) throw std::invalid_argument("meshSmoothing: no isosurface has been extracted");
+    if (iterations) *iterations = mesh_smooth_iterations_;
+    if (lambda) *lambda = mesh_smooth_lambda_;
+    if (mu) *mu = mesh_smooth_mu_;
+    if (fix_boundary) *fix_boundary = mesh_smooth_fix_ ? 1 : 0;
+    if (fixed_vertices) *fixed_vertices = mesh_smooth_fixed_;
+}
+
+void RendererCore::clearMeshSmoothing()
+{
+    mesh_smooth_iterations_ = 0; mesh_smooth_lambda_ = mesh_smooth_mu_ = 0.0f; mesh_smooth_fix_ = false; mesh_smooth_fixed_ = 0;
 }
 
 void RendererCore::meshInfo(int32_t *iso, uint64_t *n_vertices, uint64_t *n_triangles) const

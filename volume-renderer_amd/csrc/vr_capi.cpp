@@ -446,6 +446,24 @@ int vr_get_simplify_ms(vr_handle h, float *ms)
     return VR_OK;
 }
 
+int vr_smooth_mesh(vr_handle h, int iterations, float lambda, float mu, int fix_boundary)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.smoothMesh(iterations, lambda, mu, fix_boundary); });
+}
+
+int vr_get_mesh_smoothing(vr_handle h, int *iterations, float *lambda, float *mu, int *fix_boundary, uint64_t *fixed_vertices)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.meshSmoothing(iterations, lambda, mu, fix_boundary, fixed_vertices); });
+}
+
+int vr_get_mesh_smooth_ms(vr_handle h, float *build_ms, float *iterate_ms)
+{
+    if (!h || (!build_ms && !iterate_ms)) return VR_E_INVALID;
+    if (build_ms) *build_ms = h->core.lastMeshSmoothBuildMs();
+    if (iterate_ms) *iterate_ms = h->core.lastMeshSmoothIterateMs();
+    return VR_OK;
+}
+
 int vr_label_components(vr_handle h, int32_t iso_value, uint64_t *n_components)
 {
     return guarded(h, [&](vr::RendererCore &c) { c.labelComponents(iso_value, n_components); });

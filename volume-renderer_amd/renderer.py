@@ -140,6 +140,9 @@ def load_library() -> C.CDLL:
         "vr_simplify_mesh": (i32, [h, f32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "vr_get_mesh_simplification": (i32, [h, C.POINTER(f32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "vr_get_simplify_ms": (i32, [h, C.POINTER(f32)]),
+        "vr_smooth_mesh": (i32, [h, i32, f32, f32, i32]),
+        "vr_get_mesh_smoothing": (i32, [h, C.POINTER(i32), C.POINTER(f32), C.POINTER(f32), C.POINTER(i32), C.POINTER(C.c_uint64)]),
+        "vr_get_mesh_smooth_ms": (i32, [h, C.POINTER(f32), C.POINTER(f32)]),
         "vr_label_components": (i32, [h, i32, C.POINTER(C.c_uint64)]),
         "vr_get_components_info": (i32, [h, C.POINTER(i32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "vr_read_components": (i32, [h, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_uint64]),
@@ -741,6 +744,26 @@ class RendererCore:
         ms = C.c_float(0.0)
         self._check(self._lib.vr_get_simplify_ms(self._h, C.byref(ms)))
         return float(ms.value)
+
+    def smoothMesh(self, iterations=10, lam=0.5, mu=-0.53, fix_boundary=True) -> int:
+        """vr_smooth_mesh: Taubin's lambda|mu smoothing of the resident mesh's positions (`iterations` times a step towards the
+        neighbours' mean with factor `lam`, then one with factor `mu`; mu = 0: plain Laplacian), the normals recomputed from the
+        result, the triangles untouched; with fix_boundary the ends of edges with one triangle stay.  Calls accumulate.
+        Returns the number of fixed vertices."""
+        self._check(self._lib.vr_smooth_mesh(self._h, int(iterations), C.c_float(float(lam)), C.c_float(float(mu)), 1 if fix_boundary else 0))
+        return self.meshSmoothing()["fixed_vertices"]
+
+    def meshSmoothing(self) -> dict:
+        """the last smoothMesh on the resident mesh: dict(iterations, lam, mu, fix_boundary, fixed_vertices); all 0 on a new mesh"""
+        it, lam, mu, fix, fixed = C.c_int32(0), C.c_float(0.0), C.c_float(0.0), C.c_int32(0), C.c_uint64(0)
+        self._check(self._lib.vr_get_mesh_smoothing(self._h, C.byref(it), C.byref(lam), C.byref(mu), C.byref(fix), C.byref(fixed)))
+        return dict(iterations=int(it.value), lam=float(lam.value), mu=float(mu.value), fix_boundary=bool(fix.value), fixed_vertices=int(fixed.value))
+
+    def meshSmoothMs(self) -> dict:
+        """HIP-event times of the last smoothMesh, ms: dict(build_ms, iterate_ms) -- the graph, and the steps and normals"""
+        build, iterate = C.c_float(0.0), C.c_float(0.0)
+        self._check(self._lib.vr_get_mesh_smooth_ms(self._h, C.byref(build), C.byref(iterate)))
+        return dict(build_ms=float(build.value), iterate_ms=float(iterate.value))
 
     def labelComponents(self, iso) -> int:
         """vr_label_components: the connected components of the voxels s >= iso of the volume being rendered (14-neighbourhood of
