@@ -1001,7 +1001,7 @@ void RendererCore::residentBytes(uint64_t &volume, uint64_t &copies, uint64_t &o
     volume = d_vol_.bytes();
     copies = copies_.copiesBytes();
     other = d_fb_.bytes() + d_tf_.bytes() + d_spp_.bytes() + d_scratch_.bytes() + d_depth_.bytes() + d_values_.bytes() + copies_.skipGridBytes() +
-            d_loaded_.bytes() + meshBytes() + d_labels_.bytes() + d_rgba8_.bytes() + tiles_.bytes();
+            d_loaded_.bytes() + mesh_.bytes() + comp_.labels.bytes() + d_rgba8_.bytes() + tiles_.bytes();
     for (const auto &q : d_present_) other += q.bytes();
 }
 
@@ -1095,10 +1095,10 @@ hipError_t RendererCore::launchKernel(const PreparedLaunch &F, uint32_t *spp)
 }
 
 // iso_s = float(iso + 1000) for 16-bit data under VR_QUIRK_U16_OFFSET (the window's own offset, setMinVal), float(iso) otherwise
-float RendererCore::isoStored() const
+float RendererCore::storedIso(int32_t iso) const
 {
     const bool offset = datasize_bytes == 2 && (quirks & kQuirkU16Offset);
-    return (float)((int64_t)iso_value_ + (offset ? 1000 : 0));
+    return (float)((int64_t)iso + (offset ? 1000 : 0));
 }
 
 void RendererCore::readDepth(float *depth, size_t n_floats)

@@ -18,15 +18,14 @@
 #include "launch_plan.h"
 #include "launch_tuner.h"
 #include "tile_tables.h"
+#include "mesh_files.h"
 #include "volume_copies.h"
+#include "volume_ops.h"
 #include "vr_frame.h"
 
 namespace vr {
 
 struct NoDeviceError : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
-struct IoError : std::runtime_error {
     using std::runtime_error::runtime_error;
 };
 
@@ -173,7 +172,7 @@ public:
     // triangles: a queued message and std::invalid_argument; an allocation that fails: DeviceMemoryError; in each case the
     // previous mesh stays.  No rendering state changes.
     void extractIsosurface(int32_t iso, uint64_t *n_vertices, uint64_t *n_triangles);
-    bool hasMesh() const { return mesh_valid_; }
+    bool hasMesh() const { return mesh_.valid; }
     void meshInfo(int32_t *iso, uint64_t *n_vertices, uint64_t *n_triangles) const;
     void readMesh(float *positions, float *normals, uint32_t *triangles, uint64_t vertex_capacity, uint64_t triangle_capacity);
     void saveMesh(const std::string &fn, const std::string &ext);   // "stl" (binary) | "ply" (binary little endian)
@@ -211,14 +210,14 @@ public:
     // std::invalid_argument; an allocation that fails: DeviceMemoryError; a capped loop in a kernel: HipError; in each case the
     // previous labelling stays.  No rendering state changes.
     void labelComponents(int32_t iso, uint64_t *n_components);
-    bool hasComponents() const { return comp_valid_; }
-    void componentsInfo(int32_t *iso, uint64_t *n_components, uint64_t *n_inside, uint64_t *n_selected) const;
-    void readComponents(uint64_t *voxels, uint64_t *first_voxel, int32_t *bbox6, uint8_t *selected, uint64_t capacity) const;
+    bool hasComponents() const { return comp_.records.valid; }
+    void componentsInfo(int32_t *iso, uint64_t *n_components, uint64_t *n_inside, uint64_t *n_selected) const { comp_.records.info(iso, n_components, n_inside, n_selected); }
+    void readComponents(uint64_t *voxels, uint64_t *first_voxel, int32_t *bbox6, uint8_t *selected, uint64_t capacity) const { comp_.records.read(voxels, first_voxel, bbox6, selected, capacity); }
     void readLabels(uint32_t *labels, uint64_t n_voxels);
     uint32_t componentAt(int i, int j, int k);
     // selected: voxels >= min_voxels and, when keep_largest > 0, among the keep_largest first by (voxels descending, label ascending)
-    uint64_t selectComponents(uint64_t min_voxels, uint64_t keep_largest);
-    uint64_t selectComponentList(const uint32_t *labels, uint64_t n);   // exactly these; a label of 0 or above n_components: std::invalid_argument, nothing changes
+    uint64_t selectComponents(uint64_t min_voxels, uint64_t keep_largest) { return comp_.records.select(min_voxels, keep_largest); }
+    uint64_t selectComponentList(const uint32_t *labels, uint64_t n) { return comp_.records.selectList(labels, n); }   // exactly these; a label of 0 or above n_components: std::invalid_argument, nothing changes
     // extractIsosurface at the labelling's iso value with INSIDE meaning "inside and its component selected": replaces the mesh
     void extractComponents(uint64_t *n_vertices, uint64_t *n_triangles);
     void freeComponents();
@@ -253,35 +252,26 @@ private:
     DeviceBuffer<uint8_t> d_loaded_;         // while d_vol_ is a smoothed volume: the loaded one (same dimensions, type and layout)
     float smooth_sigma_[3] = {0.0f, 0.0f, 0.0f};
     float last_smooth_ms_ = 0.0f;
-    bool mesh_valid_ = false;                // an extraction has succeeded (its mesh may be empty) and was not freed
-    int32_t mesh_iso_ = 0;
-    uint64_t mesh_nv_ = 0, mesh_nt_ = 0;
-    DeviceBuffer<float> d_mesh_pos_, d_mesh_nrm_;   // 3 floats a vertex
-    DeviceBuffer<uint32_t> d_mesh_tri_;      // 3 indices a triangle
-    float last_mesh_ms_ = 0.0f;
-    float mesh_cell_ = 0.0f;                 // meshSimplification
-    uint64_t mesh_src_nv_ = 0, mesh_src_nt_ = 0;
-    float last_simplify_ms_ = 0.0f;
-    int mesh_smooth_iterations_ = 0;         // meshSmoothing
-    float mesh_smooth_lambda_ = 0.0f, mesh_smooth_mu_ = 0.0f;
-    bool mesh_smooth_fix_ = false;
-    uint64_t mesh_smooth_fixed_ = 0;
+    ResidentMesh mesh_;                      // the extracted mesh with its simplification and smoothing records (resident_mesh.h)
+    float last_mesh_ms_ = 0.0f, last_simplify_ms_ = 0.0f;
     float last_mesh_smooth_build_ms_ = 0.0f, last_mesh_smooth_iterate_ms_ = 0.0f;
-    void clearMeshSmoothing();
-    uint64_t meshBytes() const;              // device bytes of the mesh
-    // the shared body of extractIsosurface and extractComponents; selected: launch_components_plane's bits or nullptr; ms: kernel time so far
+    // the shared body of extractIsosurface and extractComponents; selected: selection_plane's bits or nullptr; ms: kernel time so far
     void extractMesh(int32_t iso, float iso_s, const uint64_t *selected, float ms, uint64_t *n_vertices, uint64_t *n_triangles);
-    bool comp_valid_ = false;                // a labelling has succeeded (it may have no component) and was not dropped
-    int32_t comp_iso_ = 0;
-    float comp_iso_s_ = 0.0f;                // the iso value in stored units when the labelling was made
+    Labelling comp_;                         // the labelling: records on the host (component_records.h), labels on the device
     int comp_index_bits_ = 0;                // setComponentIndexBits
-    DeviceBuffer<uint32_t> d_labels_;        // one label per voxel, linear order
-    std::vector<uint64_t> comp_voxels_, comp_first_;   // the records, entry label - 1
-    std::vector<int32_t> comp_bbox_;         // 6 each
-    std::vector<uint8_t> comp_selected_;
-    uint64_t comp_inside_ = 0;
     float last_comp_ms_ = 0.0f;
-    hipError_t finishTimed(hipError_t e, float &ms);   // ends a stretch of kernels that began with ev0_ recorded, once `e` says they were all launched
+    DeviceQueue queue() const { return {stream(), ev0_, ev1_}; }   // what the algorithms of volume_ops.h launch on and time with
+    // runs one of them: a RefusalWithMessage queues its message for the GUI and goes on as it is
+    template <class F>
+    auto queueingRefusals(F &&call) -> decltype(call())
+    {
+        try {
+            return call();
+        } catch (const RefusalWithMessage &r) {
+            setMessage("Error!", r.message);
+            throw;
+        }
+    }
     // geometry and voxel type of the volume that is RESIDENT (set only after a successful upload).
     // tex3D_dim / datasize_bytes above are GUI inputs of readVolumeData, like the reference's fields;
     // the reference's shader reads textureSize() of the uploaded texture (VolumeRenderer.cs:62), not them.
@@ -301,7 +291,8 @@ private:
     int32_t iso_value_ = 0;
     DeviceBuffer<float> d_depth_;            // depth target of the iso frames (+inf where no surface; allocated on the first one)
     int depth_rows_ = -1, depth_w_ = 0;      // rows x width the last iso frame's depth is indexed by (-1: no iso frame yet)
-    float isoStored() const;                 // the iso value in stored voxel units (the +1000 of VR_QUIRK_U16_OFFSET included)
+    float storedIso(int32_t iso) const;      // an iso value in stored voxel units (the +1000 of VR_QUIRK_U16_OFFSET included)
+    float isoStored() const { return storedIso(iso_value_); }   // ... the isosurface mode's
     bool reslice_enable_ = false;
     float reslice_geom_[12] = {};            // o, du, dv, dw (vr_reslice.h: ResliceGeom)
     int reslice_mode_ = 0, reslice_n_ = 1;   // VR_SLAB_*, slab samples
@@ -381,7 +372,6 @@ private:
     void dropDerived();                      // everything built from the voxels of d_vol_: packed copy, apron copies, skip grid, the tile order under skipping
     void allocVolume(int nx, int ny, int nz, int bytes, int layout);
     DeviceBuffer<uint8_t> allocVolumeBuffer(int nx, int ny, int nz, int bytes, int layout);   // allocVolume's storage contract: zeroed brick padding, the slack slab
-    void smoothPasses(const void *src, void *dst, const float sigma[3]);
     size_t storageVoxels(int nx, int ny, int nz, int layout) const;
     void afterVolumeLoaded(const std::string &name);
     void scanDatasetRange();

@@ -11,7 +11,7 @@ namespace vr {
 // One labelling.  Voxel numbers are linear indices i + nx * (j + ny * k) whatever the volume's layout.
 //   parent: one index per voxel, index_bits wide (32: uint32_t, 64: uint64_t); all ones for an outside voxel.
 //   bits:   one bit per voxel in linear order, 64 to a word (component_words): the voxel is a root -- its component's first voxel.
-//   scan:   component_words + 1 words: the roots of each word, scanned exclusively in place by launch_mesh_scan; the last word
+//   scan:   component_words + 1 words: the roots of each word, scanned exclusively in place by launch_scan64; the last word
 //           then holds the number of components.
 //   labels: one uint32 per voxel; with 32-bit parents this may be the parent array itself (the labels replace it in place).
 //   error:  one word, zeroed by the caller; a kernel ORs a kComponents* bit into it instead of looping without bound.

@@ -12,7 +12,7 @@ namespace vr {
 // z1 - 1 reference vertices that the voxels of plane z1 own and the next slab writes.
 //   scan: (zs - z0) * nx * ny + 1 words, x fastest.  After count: low half = vertices the voxel owns (0 .. 7), high half =
 //         triangles of the cell whose origin the voxel is (0 .. 12; 0 outside [z0, z1)); the last word is 0.  The host scans
-//         it exclusively in place (launch_mesh_scan), which needs both halves' sums below 2^32: kMeshMaxSlabVoxels.
+//         it exclusively in place (vr_primitives.h: launch_scan64), which needs both halves' sums below 2^32: kMeshMaxSlabVoxels.
 //   mask: one byte per voxel of the same planes: bit d = the voxel's edge in direction d carries a vertex.
 struct MeshSlab {
     const void *volume;                 // allocVolume's storage
@@ -39,9 +39,6 @@ inline int mesh_scan_planes(const MeshSlab &S) { return (S.z1 + 1 < S.nz ? S.z1 
 inline uint64_t mesh_scan_words(const MeshSlab &S) { return (uint64_t)mesh_scan_planes(S) * (uint64_t)S.nx * (uint64_t)S.ny + 1; }
 
 hipError_t launch_mesh_count(const MeshSlab &S, hipStream_t st);
-// exclusive scan of `words` packed counts in place; temp: device scratch of at least mesh_scan_temp_bytes(words)
-size_t mesh_scan_temp_bytes(uint64_t words);
-hipError_t launch_mesh_scan(uint64_t *scan, uint64_t words, void *temp, size_t temp_bytes, hipStream_t st);
 hipError_t launch_mesh_emit(const MeshSlab &S, hipStream_t st);
 
 }  // namespace vr

@@ -7,7 +7,7 @@
 // Shape: three launches per z slab, one thread per voxel, no atomics (the mesh is the same bytes on every run).
 //   count: per voxel, the directions whose edge carries a vertex (a mask byte) and, packed into one 64-bit word, the number of
 //          those vertices (low half) and of the triangles of the cell the voxel is the origin of (high half).
-//   scan:  rocPRIM's exclusive scan of the words, in place: both offsets at once.  The totals are known before the mesh is allocated.
+//   scan:  the exclusive scan (vr_primitives.h) of the words, in place: both offsets at once.  The totals are known before the mesh is allocated.
 //   emit:  the voxel's vertices at its vertex offset, its cell's triangles at its triangle offset.  The index of a vertex on
 //          edge (A, d) is A's offset plus the number of A's active directions below d.
 // Every voxel is read straight from the volume (eight corner loads per thread, neighbours served by the caches): no LDS
@@ -25,8 +25,6 @@
 
 #if VR_MESH_TU == 0
 #include <cstring>
-
-#include <rocprim/device/device_scan.hpp>
 #endif
 
 namespace vr {
@@ -352,7 +350,7 @@ VR_CODE_UNIT(mesh, VR_MESH_TU, "extraction", WARM_LOAD_SHADER)
 #if VR_MESH_TU == 1
 hipError_t launch_mesh_u16(const MeshSlab &S, bool emit, hipStream_t st) { return launch_mesh_type<uint16_t>(S, emit, st); }
 #else
-// the unit of 8-bit volumes also carries the entry points and the scan
+// the unit of 8-bit volumes also carries the entry points
 hipError_t launch_mesh_u8(const MeshSlab &S, bool emit, hipStream_t st) { return launch_mesh_type<uint8_t>(S, emit, st); }
 hipError_t launch_mesh_u16(const MeshSlab &S, bool emit, hipStream_t st);
 
@@ -380,20 +378,6 @@ hipError_t launch_mesh_emit(const MeshSlab &S, hipStream_t st)
 {
     if (!slab_ok(S, true)) return hipErrorInvalidValue;
     return S.bytes_per_voxel == 1 ? launch_mesh_u8(S, true, st) : launch_mesh_u16(S, true, st);
-}
-
-size_t mesh_scan_temp_bytes(uint64_t words)
-{
-    size_t bytes = 0;
-    uint64_t *none = nullptr;
-    if (rocprim::exclusive_scan(nullptr, bytes, none, none, (uint64_t)0, (size_t)words, rocprim::plus<uint64_t>()) != hipSuccess) return 0;
-    return bytes;
-}
-
-hipError_t launch_mesh_scan(uint64_t *scan, uint64_t words, void *temp, size_t temp_bytes, hipStream_t st)
-{
-    if (!scan || !temp || words == 0) return hipErrorInvalidValue;
-    return rocprim::exclusive_scan(temp, temp_bytes, scan, scan, (uint64_t)0, (size_t)words, rocprim::plus<uint64_t>(), st);
 }
 #endif
 

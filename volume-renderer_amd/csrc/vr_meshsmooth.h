@@ -1,7 +1,8 @@
 // vr_meshsmooth.h -- host-callable launchers of the mesh smoothing kernels (vr_meshsmooth.hip, vr_smooth_mesh): Taubin's
 // lambda|mu filter on the resident mesh's vertex graph and the normals of the result.  The definition, step by step, is in
 // include/vr_core.h and DESIGN.md section 1.8; tests/mesh_smooth_ref/mesh_smooth_ref.c restates it on the CPU.
-// RendererCore::smoothMesh (volume_ops.cpp) owns the arrays and the order of the launches; nothing here allocates or waits.
+// smooth_mesh (mesh_smooth.cpp) owns the arrays and the order of the launches, the sorts and scans between them are
+// vr_primitives.h's; nothing here allocates or waits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,16 +14,6 @@ constexpr uint64_t kMeshSmoothIgnoredPair = ~0ull;        // the key of a pair w
 
 // key[6 t + q] = a << vb | b for the six directed pairs of triangle t (vb = the bits of nv - 1), all ones where a == b
 hipError_t launch_meshsmooth_pairs(const uint32_t *triangles, uint64_t nt, uint32_t vb, uint64_t *key, hipStream_t st);
-// radix sorts over the key bits [0, bits): of keys alone (64-bit), and stably of (key, value) pairs (32-bit)
-size_t meshsmooth_sort_keys_temp_bytes(uint64_t n, uint32_t bits);
-size_t meshsmooth_sort_pairs_temp_bytes(uint64_t n, uint32_t bits);
-hipError_t launch_meshsmooth_sort_keys(void *temp, size_t temp_bytes, const uint64_t *key_in, uint64_t *key_out, uint64_t n, uint32_t bits,
-                                       hipStream_t st);
-hipError_t launch_meshsmooth_sort_pairs(void *temp, size_t temp_bytes, const uint32_t *key_in, uint32_t *key_out, const uint32_t *value_in,
-                                        uint32_t *value_out, uint64_t n, uint32_t bits, hipStream_t st);
-// exclusive sums of n uint32 in place (their total stays below 2^32)
-size_t meshsmooth_scan_temp_bytes(uint64_t n);
-hipError_t launch_meshsmooth_scan(uint32_t *data, uint64_t n, void *temp, size_t temp_bytes, hipStream_t st);
 // head[i] = 1 where sorted key i is a pair and differs from key i - 1 (head: n + 1 words, the last one 0); with `fixed` not null
 // fixed[a] = 1 for a run of length 1 (fixed: zeroed by the caller; every writer stores the same value)
 hipError_t launch_meshsmooth_heads(const uint64_t *key_sorted, uint64_t n, uint32_t vb, uint32_t *head, uint32_t *fixed, hipStream_t st);

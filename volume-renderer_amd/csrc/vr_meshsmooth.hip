@@ -4,9 +4,9 @@
 // tests/mesh_smooth_ref/mesh_smooth_ref.c restates it on the CPU and tests/test_mesh_smooth_gpu.py holds these kernels to it bit
 // for bit.  No float is ever added atomically: every sum runs in the definition's order inside one thread.
 //
-// One translation unit: nothing here reads a voxel.  Shape (RendererCore::smoothMesh launches them in this order):
+// One translation unit: nothing here reads a voxel.  Shape (smooth_mesh, mesh_smooth.cpp, launches them in this order):
 //   pairs:    per triangle, its six directed pairs as keys a << vb | b; a pair with equal ends is all ones.
-//   sort:     rocPRIM's radix sort of the keys over the 2 vb bits in use: a vertex's pairs are adjacent, ascending by neighbour,
+//   sort:     the radix sort (vr_primitives.h) of the keys over the 2 vb bits in use: a vertex's pairs are adjacent, ascending by neighbour,
 //             equal pairs in a run whose length is the edge's multiplicity; the ignored pairs come last.
 //   heads:    the first of every run; a run of length 1 marks its first end FIXED (its other end is marked by the reverse pair).
 //   rows:     an exclusive scan of the heads compacts the neighbours; the first and the last pair of a vertex write its row's
@@ -20,9 +20,6 @@
 // Element numbers are 64-bit and grids two-dimensional: 6 T may be 2^32 - 1.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include "vr_code_unit.h"
 #include "vr_meshsmooth.h"
@@ -165,50 +162,6 @@ hipError_t launch_meshsmooth_pairs(const uint32_t *triangles, uint64_t nt, uint3
     if (!triangles || !key || nt == 0 || 6 * nt > kMeshSmoothMaxPairs || vb > 32) return hipErrorInvalidValue;
     hipLaunchKernelGGL(meshsmooth_pairs_kernel, grid_of(nt), dim3(256), 0, st, triangles, nt, vb, key);
     return hipGetLastError();
-}
-
-size_t meshsmooth_sort_keys_temp_bytes(uint64_t n, uint32_t bits)
-{
-    size_t bytes = 0;
-    uint64_t *k = nullptr;
-    if (rocprim::radix_sort_keys(nullptr, bytes, (const uint64_t *)k, k, (size_t)n, 0u, bits) != hipSuccess) return 0;
-    return bytes;
-}
-
-size_t meshsmooth_sort_pairs_temp_bytes(uint64_t n, uint32_t bits)
-{
-    size_t bytes = 0;
-    uint32_t *k = nullptr, *v = nullptr;
-    if (rocprim::radix_sort_pairs(nullptr, bytes, (const uint32_t *)k, k, (const uint32_t *)v, v, (size_t)n, 0u, bits) != hipSuccess) return 0;
-    return bytes;
-}
-
-hipError_t launch_meshsmooth_sort_keys(void *temp, size_t temp_bytes, const uint64_t *key_in, uint64_t *key_out, uint64_t n, uint32_t bits,
-                                       hipStream_t st)
-{
-    if (!temp || !key_in || !key_out || n == 0 || bits == 0 || bits > 64) return hipErrorInvalidValue;
-    return rocprim::radix_sort_keys(temp, temp_bytes, key_in, key_out, (size_t)n, 0u, bits, st);
-}
-
-hipError_t launch_meshsmooth_sort_pairs(void *temp, size_t temp_bytes, const uint32_t *key_in, uint32_t *key_out, const uint32_t *value_in,
-                                        uint32_t *value_out, uint64_t n, uint32_t bits, hipStream_t st)
-{
-    if (!temp || !key_in || !key_out || !value_in || !value_out || n == 0 || bits == 0 || bits > 32) return hipErrorInvalidValue;
-    return rocprim::radix_sort_pairs(temp, temp_bytes, key_in, key_out, value_in, value_out, (size_t)n, 0u, bits, st);
-}
-
-size_t meshsmooth_scan_temp_bytes(uint64_t n)
-{
-    size_t bytes = 0;
-    uint32_t *none = nullptr;
-    if (rocprim::exclusive_scan(nullptr, bytes, none, none, 0u, (size_t)n, rocprim::plus<uint32_t>()) != hipSuccess) return 0;
-    return bytes;
-}
-
-hipError_t launch_meshsmooth_scan(uint32_t *data, uint64_t n, void *temp, size_t temp_bytes, hipStream_t st)
-{
-    if (!data || !temp || n == 0) return hipErrorInvalidValue;
-    return rocprim::exclusive_scan(temp, temp_bytes, data, data, 0u, (size_t)n, rocprim::plus<uint32_t>(), st);
 }
 
 hipError_t launch_meshsmooth_heads(const uint64_t *key_sorted, uint64_t n, uint32_t vb, uint32_t *head, uint32_t *fixed, hipStream_t st)

@@ -1,7 +1,7 @@
 // vr_simplify.h -- host-callable launchers of the mesh simplification kernels (vr_simplify.hip, vr_simplify_mesh): vertex
 // clustering on a grid of cubic cells.  The definition, step by step, is in include/vr_core.h and DESIGN.md section 1.7;
-// tests/simplify_ref/simplify_ref.c restates it on the CPU.  RendererCore::simplifyMesh (volume_ops.cpp) owns the arrays and
-// the order of the launches; nothing here allocates or waits.
+// tests/simplify_ref/simplify_ref.c restates it on the CPU.  simplify_mesh (mesh_simplify.cpp) owns the arrays and the order of
+// the launches, the sorts and scans between them are vr_primitives.h's; nothing here allocates or waits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,16 +16,6 @@ hipError_t launch_simplify_extent(const float *positions, uint64_t nv, float cel
 // key[v] = c_x | c_y << bx | c_z << (bx + by) (bx, by: bits the extent needs), index[v] = v, dist[v] = step 3's dist as bits
 hipError_t launch_simplify_keys(const float *positions, uint64_t nv, float cell, uint32_t bx, uint32_t by, uint64_t *key, uint32_t *index,
                                 uint32_t *dist, hipStream_t st);
-// stable radix sorts of (key, value) pairs over the key bits [0, bits); temp: device scratch of at least the _temp_bytes
-size_t simplify_sort64_temp_bytes(uint64_t n, uint32_t bits);
-size_t simplify_sort32_temp_bytes(uint64_t n, uint32_t bits);
-hipError_t launch_simplify_sort64(void *temp, size_t temp_bytes, const uint64_t *key_in, uint64_t *key_out, const uint32_t *value_in,
-                                  uint32_t *value_out, uint64_t n, uint32_t bits, hipStream_t st);
-hipError_t launch_simplify_sort32(void *temp, size_t temp_bytes, const uint32_t *key_in, uint32_t *key_out, const uint32_t *value_in,
-                                  uint32_t *value_out, uint64_t n, uint32_t bits, hipStream_t st);
-// sums of n uint32 in place (their total stays below 2^32): inclusive, and exclusive
-size_t simplify_scan_temp_bytes(uint64_t n);
-hipError_t launch_simplify_scan(uint32_t *data, uint64_t n, bool inclusive, void *temp, size_t temp_bytes, hipStream_t st);
 // head[i] = 1 where sorted key i differs from key i - 1 (and at 0): its inclusive sums minus 1 number the clusters in key order
 hipError_t launch_simplify_heads(const uint64_t *key_sorted, uint64_t nv, uint32_t *head, hipStream_t st);
 // cluster[v] for every vertex, and winner[cluster] = min over its vertices of dist << 32 | v (winner: all bits set by the caller)

@@ -4,11 +4,11 @@
 // include/vr_core.h and DESIGN.md section 1.7; tests/simplify_ref/simplify_ref.c restates it on the CPU and
 // tests/test_simplify_gpu.py holds these kernels to it bit for bit.
 //
-// One translation unit: nothing here reads a voxel.  Shape (RendererCore::simplifyMesh launches them in this order):
+// One translation unit: nothing here reads a voxel.  Shape (simplify_mesh, mesh_simplify.cpp, launches them in this order):
 //   extent:   per vertex, the three cell indices; their maxima per axis (a fixed grid striding over the vertices, one atomic a
 //             wavefront) size the packed key.
 //   keys:     per vertex, the packed cell key, the vertex index and the bits of dist.
-//   sort:     rocPRIM's stable radix sort of (key, index) over the key bits in use; run heads + an inclusive scan number the
+//   sort:     the stable radix sort (vr_primitives.h) of (key, index) over the key bits in use; run heads + an inclusive scan number the
 //             clusters in key order.
 //   winners:  a 64-bit atomicMin of dist << 32 | index per cluster: non-negative fp32 bit patterns order like their values
 //             and the minimum does not depend on the order of arrival, so the result is the same on every run.
@@ -20,9 +20,6 @@
 // Element numbers are 64-bit and grids two-dimensional: a mesh may have 2^32 - 1 triangles, three indices each.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include "vr_code_unit.h"
 #include "vr_simplify.h"
@@ -209,53 +206,6 @@ hipError_t launch_simplify_keys(const float *positions, uint64_t nv, float cell,
     if (!positions || !key || !index || !dist || nv == 0 || nv > kSimplifyMaxCount || bx > 21 || by > 21) return hipErrorInvalidValue;
     hipLaunchKernelGGL(simplify_keys_kernel, grid_of(nv), dim3(256), 0, st, positions, nv, cell, bx, by, key, index, dist);
     return hipGetLastError();
-}
-
-size_t simplify_sort64_temp_bytes(uint64_t n, uint32_t bits)
-{
-    size_t bytes = 0;
-    uint64_t *k = nullptr;
-    uint32_t *v = nullptr;
-    if (rocprim::radix_sort_pairs(nullptr, bytes, (const uint64_t *)k, k, (const uint32_t *)v, v, (size_t)n, 0u, bits) != hipSuccess) return 0;
-    return bytes;
-}
-
-size_t simplify_sort32_temp_bytes(uint64_t n, uint32_t bits)
-{
-    size_t bytes = 0;
-    uint32_t *k = nullptr, *v = nullptr;
-    if (rocprim::radix_sort_pairs(nullptr, bytes, (const uint32_t *)k, k, (const uint32_t *)v, v, (size_t)n, 0u, bits) != hipSuccess) return 0;
-    return bytes;
-}
-
-hipError_t launch_simplify_sort64(void *temp, size_t temp_bytes, const uint64_t *key_in, uint64_t *key_out, const uint32_t *value_in,
-                                  uint32_t *value_out, uint64_t n, uint32_t bits, hipStream_t st)
-{
-    if (!temp || !key_in || !key_out || !value_in || !value_out || n == 0 || bits == 0 || bits > 64) return hipErrorInvalidValue;
-    return rocprim::radix_sort_pairs(temp, temp_bytes, key_in, key_out, value_in, value_out, (size_t)n, 0u, bits, st);
-}
-
-hipError_t launch_simplify_sort32(void *temp, size_t temp_bytes, const uint32_t *key_in, uint32_t *key_out, const uint32_t *value_in,
-                                  uint32_t *value_out, uint64_t n, uint32_t bits, hipStream_t st)
-{
-    if (!temp || !key_in || !key_out || !value_in || !value_out || n == 0 || bits == 0 || bits > 32) return hipErrorInvalidValue;
-    return rocprim::radix_sort_pairs(temp, temp_bytes, key_in, key_out, value_in, value_out, (size_t)n, 0u, bits, st);
-}
-
-size_t simplify_scan_temp_bytes(uint64_t n)
-{
-    size_t a = 0, b = 0;
-    uint32_t *none = nullptr;
-    if (rocprim::exclusive_scan(nullptr, a, none, none, 0u, (size_t)n, rocprim::plus<uint32_t>()) != hipSuccess) return 0;
-    if (rocprim::inclusive_scan(nullptr, b, none, none, (size_t)n, rocprim::plus<uint32_t>()) != hipSuccess) return 0;
-    return a > b ? a : b;
-}
-
-hipError_t launch_simplify_scan(uint32_t *data, uint64_t n, bool inclusive, void *temp, size_t temp_bytes, hipStream_t st)
-{
-    if (!data || !temp || n == 0) return hipErrorInvalidValue;
-    if (inclusive) return rocprim::inclusive_scan(temp, temp_bytes, data, data, (size_t)n, rocprim::plus<uint32_t>(), st);
-    return rocprim::exclusive_scan(temp, temp_bytes, data, data, 0u, (size_t)n, rocprim::plus<uint32_t>(), st);
 }
 
 hipError_t launch_simplify_heads(const uint64_t *key_sorted, uint64_t nv, uint32_t *head, hipStream_t st)
