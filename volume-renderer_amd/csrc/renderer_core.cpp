@@ -363,8 +363,11 @@ void RendererCore::computeHistogram(float out[256])
     // (16-bit) or -1 (8-bit) and is raised to the largest bin count
     double max_value = res_bytes_ == 2 ? (double)max_dataset_val : -1.0;
     for (int i = 1; i < 256; i++) max_value = std::max(max_value, (double)counts[i]);
+    // a volume of zeros (X, the voxel the range scan skips, apart): the normaliser is 0 and the reference's own arithmetic is
+    // undefined; every bin is 0 here (deviations)
+    const bool empty = !(max_value > 0.0);
     for (int i = 0; i < 256; i++) {
-        histogram[i] = i == 0 ? 0.0f : (float)counts[i] * 100.0f / (float)max_value;
+        histogram[i] = (i == 0 || empty) ? 0.0f : (float)counts[i] * 100.0f / (float)max_value;
         out[i] = histogram[i];
     }
 }
