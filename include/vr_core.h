@@ -296,6 +296,50 @@ int vr_set_smoothing_workspace(vr_handle h, uint64_t bytes);
 /* measurement aid: HIP-event time, in ms, of the passes of the last vr_smooth_volume that ran any (first launch to last,
    every slab; allocations, the range scan and host work excluded); 0 before the first and after a call that ran none */
 int vr_get_smoothing_ms(vr_handle h, float *ms);
+/* Grey-level morphology and the median of the resident volume, computed on the device (no reference equivalent; 3D Slicer's
+   Segment Editor "Smoothing" -- median, opening, closing -- and "Margin" -- grow, shrink; VTK's vtkImageContinuousErode3D,
+   vtkImageContinuousDilate3D and vtkImageMedian3D): what goes between a threshold and the components.  A median removes
+   salt-and-pepper voxels, which a Gaussian smears into the surface, and keeps edges; an opening cuts thin bridges and a closing
+   fills pinholes without moving the iso level.  All five are rank filters on integers, so the result is defined bit for bit
+   with no rounding rule:
+   1. Window.  The window of voxel (i, j, k) is the box of (2rx+1)(2ry+1)(2rz+1) values
+      in[clamp(i+a, 0, nx-1), clamp(j+b, 0, ny-1), clamp(k+c, 0, nz-1)] for |a| <= rx, |b| <= ry, |c| <= rz: edges clamp like
+      the sampler and the Gaussian; x is the fastest axis; the values are the raw stored voxels compared as UNSIGNED integers.
+   2. Single operations.  VR_RANK_ERODE is the window's minimum, VR_RANK_DILATE its maximum, VR_RANK_MEDIAN the element at
+      0-based position (n-1)/2 of the window's n values in ascending order; n is always odd, so nothing is averaged.
+   3. Two-stage operations.  VR_RANK_OPEN is ERODE, then DILATE of that result with the same box; VR_RANK_CLOSE is DILATE, then
+      ERODE.  The second stage clamps at the edges of the first stage's OUTPUT.
+   4. Arguments.  op in 0 .. 5; every radius in 0 .. 8 for ERODE, DILATE, OPEN and CLOSE, in 0 .. 1 for MEDIAN (windows from
+      3x1x1 to 3x3x3; rz = 0 is the 3x3 in-plane median of anisotropic CT); anything else is VR_E_INVALID and changes nothing.
+      VR_RANK_OFF, or all radii 0, is the identity, and the state then reads back (VR_RANK_OFF, 0, 0, 0).  Without a volume:
+      VR_E_INVALID; a host-only handle: VR_E_NO_DEVICE; a device allocation that fails: VR_E_NOMEM -- as vr_smooth_volume, and
+      after a failure the handle keeps rendering what it rendered before.
+   5. Composition with the Gaussian.  The volume being rendered is always G(R(loaded)): R the rank filter in force, G
+      vr_smooth_volume's sigmas in force, applied by its own definition to R's voxels.  Either call recomputes from the volume
+      AS LOADED: nothing accumulates and the order of the two calls does not matter.  (VR_RANK_OFF) together with (0, 0, 0)
+      renders the loaded volume again, bit for bit.  With the rank filter off vr_smooth_volume is exactly what it is without
+      this call.  A load, vr_set_volume and vr_generate_synthetic reset both.
+   6. Everything else follows vr_smooth_volume.  Kept: the window, camera, modes, transfer function, the launch stream, the
+      launch choices and the resident mesh.  Rebuilt or invalidated as a fresh load leaves them: both ranges, the packed copy,
+      the apron copies, the skip grid, the tile order under skipping and the ray stream.  The labelling is dropped.
+      vr_read_volume, vr_histogram and vr_get_dataset_range report the rendered volume.  The loaded volume counts under
+      `other` in vr_get_resident_bytes, and vr_set_layout re-lays out both volumes without recomputing.
+   7. Memory.  Intermediates are voxel-typed whole volumes in the loaded volume's type and layout -- no fp32 copy, no z slabs: a
+      buffer is the volume's own size -- and are freed before the call returns.  Minimum and maximum are separable (one pass per
+      axis with r > 0, in the order x, y, z; OPEN and CLOSE run that twice), the median is one pass.  A call needs up to three
+      volumes' worth of free device memory (the result; one intermediate when there is more than one pass; R's voxels while a
+      Gaussian is in force, next to that Gaussian's own workspace); failure to get it is VR_E_NOMEM. */
+#define VR_RANK_OFF 0
+#define VR_RANK_ERODE 1     /* minimum over the box */
+#define VR_RANK_DILATE 2    /* maximum over the box */
+#define VR_RANK_OPEN 3      /* ERODE, then DILATE of that result, same box */
+#define VR_RANK_CLOSE 4     /* DILATE, then ERODE of that result, same box */
+#define VR_RANK_MEDIAN 5
+int vr_rank_filter_volume(vr_handle h, int op, int rx, int ry, int rz);
+int vr_get_rank_filter(vr_handle h, int *op, int r3[3]);           /* any pointer may be NULL */
+/* measurement aid, like vr_get_smoothing_ms: HIP-event time, in ms, of the passes of the last rank filter that ran any (first
+   launch to last; allocations, a Gaussian that followed, the range scan and host work excluded); 0 before the first */
+int vr_get_rank_filter_ms(vr_handle h, float *ms);
 /* Extraction of the isosurface s = iso of the resident volume -- the one being rendered, i.e. the smoothed one after
    vr_smooth_volume -- as a watertight indexed triangle mesh, computed on the device (no reference equivalent): positions in
    the units of vr_get_dims' spacing, unit normals, uint32 triangle indices.  Marching tetrahedra on the Kuhn (six-tetrahedra)

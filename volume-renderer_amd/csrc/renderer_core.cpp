@@ -195,6 +195,7 @@ void RendererCore::freeVolume()
 {
     d_vol_.reset(); d_loaded_.reset();
     smooth_sigma_[0] = smooth_sigma_[1] = smooth_sigma_[2] = 0.0f;
+    rank_op_ = 0; rank_r_[0] = rank_r_[1] = rank_r_[2] = 0;
     res_dims_[0] = res_dims_[1] = res_dims_[2] = 0; res_bytes_ = 0;
     dropDerived();
     freeComponents();                                                    // the labelling belongs to the voxels that just went

@@ -166,6 +166,13 @@ public:
     // upper bound on the bytes of ONE of smoothVolume's two fp32 plane buffers (vr_set_smoothing_workspace); 0: automatic -- the
     // whole volume's planes where they fit in 2 GiB and in the free device memory, z slabs of the volume otherwise
     uint64_t smooth_workspace_limit = 0;
+    // grey-level morphology and the median of the resident volume (vr_rank_filter_volume; vr_rank.hip).  The
+    // volume being rendered is always G(R(loaded)): R this filter, G smoothVolume's sigmas, both computed again from the volume as
+    // loaded by either call.  op outside 0 .. 5 or a radius outside 0 .. 8 (0 .. 1 for the median): std::invalid_argument; a
+    // device allocation that fails: DeviceMemoryError; either way nothing changes.  OFF or a box of one voxel reads back (OFF, 0, 0, 0).
+    void rankFilterVolume(int op, int rx, int ry, int rz);
+    void getRankFilter(int *op, int r3[3]) const { if (op) *op = rank_op_; for (int a = 0; a < 3 && r3; a++) r3[a] = rank_r_[a]; }
+    float lastRankMs() const { return last_rank_ms_; }       // HIP-event time of the last rank filter passes (first launch to last; 0: none ran)
     // extraction of the isosurface s = iso of the volume being rendered as an indexed triangle mesh (vr_extract_isosurface;
     // vr_mesh.hip).  The mesh is a snapshot on the device: it stays until the next extraction, freeMesh or the handle's end, and
     // loading or smoothing another volume leaves it alone.  No volume: std::runtime_error; more than 2^32 - 1 vertices or
@@ -248,10 +255,14 @@ private:
     int device_ = -1;
     hipStream_t own_stream_ = nullptr, user_stream_ = nullptr;
     Event ev0_, ev1_;
-    DeviceBuffer<uint8_t> d_vol_;            // the volume the kernels render: as loaded, or smoothed
-    DeviceBuffer<uint8_t> d_loaded_;         // while d_vol_ is a smoothed volume: the loaded one (same dimensions, type and layout)
+    DeviceBuffer<uint8_t> d_vol_;            // the volume the kernels render: as loaded, or rank-filtered and / or smoothed
+    DeviceBuffer<uint8_t> d_loaded_;         // while d_vol_ is a filtered volume: the loaded one (same dimensions, type and layout)
     float smooth_sigma_[3] = {0.0f, 0.0f, 0.0f};
     float last_smooth_ms_ = 0.0f;
+    int rank_op_ = 0, rank_r_[3] = {0, 0, 0};
+    float last_rank_ms_ = 0.0f;
+    // the one place that renders G(R(loaded)) for a new (op, r3, sigma): computes, swaps in, scans the ranges, adopts the state
+    void applyVolumeFilters(const char *who, int op, const int r3[3], const float sigma[3]);
     ResidentMesh mesh_;                      // the extracted mesh with its simplification and smoothing records (resident_mesh.h)
     float last_mesh_ms_ = 0.0f, last_simplify_ms_ = 0.0f;
     float last_mesh_smooth_build_ms_ = 0.0f, last_mesh_smooth_iterate_ms_ = 0.0f;

@@ -1,11 +1,12 @@
 // volume_ops.cpp -- RendererCore's members for what is computed on the resident volume and the resident mesh outside a frame:
 // each validates its arguments, calls the algorithm (volume_ops.h) with a queue and plain inputs, and adopts the result once the
-// call has returned.  Gaussian smoothing, extraction (1.5), components (1.6), simplification (1.7),
+// call has returned.  Gaussian smoothing, the rank filters (1.9), extraction (1.5), components (1.6), simplification (1.7),
 // mesh smoothing (1.8).
 #include <cmath>
 
 #include "renderer_core.h"
 #include "volume_ops.h"
+#include "rank_schedule.h"
 #include "vr_smooth.h"
 
 namespace vr {
@@ -17,20 +18,46 @@ void RendererCore::smoothVolume(float sigma_x, float sigma_y, float sigma_z)
         if (!std::isfinite(s) || s < 0.0f || s > kSmoothMaxSigma) throw std::invalid_argument("smoothVolume: every sigma must be finite and in [0, 8] voxels");
     requireDevice("smoothVolume");
     if (!d_vol_) throw std::runtime_error("smoothVolume: no dataset loaded");
+    const int r3[3] = {rank_r_[0], rank_r_[1], rank_r_[2]};
+    applyVolumeFilters("smoothVolume", rank_op_, r3, sigma);
+}
+
+void RendererCore::rankFilterVolume(int op, int rx, int ry, int rz)
+{
+    int r3[3] = {rx, ry, rz};
+    if (!rank_arguments_ok(op, r3))
+        throw std::invalid_argument("rankFilterVolume: op must be in 0 .. 5 and every radius in 0 .. 8 voxels (0 .. 1 for the median)");
+    requireDevice("rankFilterVolume");
+    if (!d_vol_) throw std::runtime_error("rankFilterVolume: no dataset loaded");
+    if (rank_is_identity(op, r3)) { op = kRankOff; r3[0] = r3[1] = r3[2] = 0; }
+    applyVolumeFilters("rankFilterVolume", op, r3, smooth_sigma_);
+}
+
+// G(R(loaded)) for the new state: R = (op, r3), already normalised to (OFF, 0, 0, 0) where it is the identity, G = sigma.
+void RendererCore::applyVolumeFilters(const char *who, int op, const int r3[3], const float sigma[3])
+{
     check(hipStreamSynchronize(stream()), "hipStreamSynchronize");      // frames in flight read the buffers replaced below
-    const bool off = sigma_x == 0.0f && sigma_y == 0.0f && sigma_z == 0.0f;
+    const bool smooth = sigma[0] != 0.0f || sigma[1] != 0.0f || sigma[2] != 0.0f, rank = op != kRankOff;
+    const bool off = !smooth && !rank;
     if (off && !d_loaded_) return;                                       // rendering the loaded volume already
     // The volume to render next: the loaded one again, or a new buffer the passes fill (freed with `next` if they throw, which waits
     // for them).  It is swapped in first and swapped back if the range scan fails, so a call that throws leaves the handle as it was.
     DeviceBuffer<uint8_t> next;
     if (!off) {
+        DeviceBuffer<uint8_t> ranked;                                    // R's voxels where G follows; freed when the passes are done
         try {
             next = allocVolumeBuffer(res_dims_[0], res_dims_[1], res_dims_[2], res_bytes_, vol_layout_);
+            if (rank && smooth) ranked = allocVolumeBuffer(res_dims_[0], res_dims_[1], res_dims_[2], res_bytes_, vol_layout_);
         } catch (const HipError &err) {
             (void)hipGetLastError();
-            throw DeviceMemoryError(err.code, std::string("smoothVolume: ") + err.what());
+            throw DeviceMemoryError(err.code, std::string(who) + ": " + err.what());
         }
-        smooth_passes(queue(), residentVolume(), d_loaded_ ? d_loaded_.get() : d_vol_.get(), next.get(), sigma, smooth_workspace_limit, last_smooth_ms_);
+        const void *src = d_loaded_ ? d_loaded_.get() : d_vol_.get();
+        if (rank) {
+            rank_passes(queue(), residentVolume(), src, smooth ? ranked.get() : next.get(), op, r3, last_rank_ms_);
+            src = ranked.get();
+        }
+        if (smooth) smooth_passes(queue(), residentVolume(), src, next.get(), sigma, smooth_workspace_limit, last_smooth_ms_);
     }
     DeviceBuffer<uint8_t> &other = off ? d_loaded_ : next;               // after the swap: the volume rendered until now
     const int keep[8] = {min_val, max_val, min_dataset_val, max_dataset_val, exact_min_, exact_max_, 0, 0};
@@ -44,9 +71,10 @@ void RendererCore::smoothVolume(float sigma_x, float sigma_y, float sigma_z)
         throw;
     }
     min_val = keep[0]; max_val = keep[1];                                // ... which is the user's and stays; no message, camera and uniforms untouched
-    if (off) d_loaded_.reset();                                          // the smoothed volume
-    else if (!d_loaded_) d_loaded_ = std::move(next);                    // (else `next` frees the earlier smoothing result)
-    for (int a = 0; a < 3; a++) smooth_sigma_[a] = sigma[a];
+    if (off) d_loaded_.reset();                                          // the filtered volume
+    else if (!d_loaded_) d_loaded_ = std::move(next);                    // (else `next` frees the earlier result)
+    for (int a = 0; a < 3; a++) { smooth_sigma_[a] = sigma[a]; rank_r_[a] = r3[a]; }
+    rank_op_ = op;
     dropDerived();                                                       // what a load leaves behind for new voxels
     freeComponents();                                                    // a labelling of the voxels rendered until now
 }

@@ -1,7 +1,7 @@
 // volume_ops.h -- the computations on the resident volume and the resident mesh outside a frame, as free functions: each sees a
 // queue and its inputs, allocates what it needs, launches its kernels and returns its result by value.  RendererCore's members
 // (volume_ops.cpp) validate, call, and adopt the result only after the function has returned: a call that throws leaves the
-// previous mesh or labelling as it was.  One file per algorithm: volume_smooth.cpp, mesh_extract.cpp, mesh_simplify.cpp,
+// previous mesh or labelling as it was.  One file per algorithm: volume_smooth.cpp, volume_rank.cpp, mesh_extract.cpp, mesh_simplify.cpp,
 // mesh_smooth.cpp, volume_components.cpp.
 #pragma once
 #include <stdexcept>
@@ -60,6 +60,8 @@ struct Labelling {
 
 // Gaussian smoothing's passes, src -> dst (both allocVolume storage of V's dimensions, type and layout); ms: set to the passes' time
 void smooth_passes(const DeviceQueue &q, const ResidentVolume &V, const void *src, void *dst, const float sigma[3], uint64_t workspace_limit, float &ms);
+// the rank filter's passes (rank_schedule.h), src -> dst like smooth_passes; op and r3 pass rank_arguments_ok and are not the identity
+void rank_passes(const DeviceQueue &q, const ResidentVolume &V, const void *src, void *dst, int op, const int r3[3], float &ms);
 // the isosurface iso_s (stored units) of V; selected: launch_components_plane's bits or nullptr; ms: kernel time so far, added to
 ResidentMesh extract_mesh(const DeviceQueue &q, const ResidentVolume &V, const float spacing[3], uint64_t workspace_limit, int32_t iso, float iso_s,
                           const uint64_t *selected, float &ms);

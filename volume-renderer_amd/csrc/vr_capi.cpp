@@ -387,6 +387,25 @@ int vr_set_smoothing_workspace(vr_handle h, uint64_t bytes)
     return VR_OK;
 }
 
+int vr_rank_filter_volume(vr_handle h, int op, int rx, int ry, int rz)
+{
+    return guarded(h, [&](vr::RendererCore &c) { c.rankFilterVolume(op, rx, ry, rz); });
+}
+
+int vr_get_rank_filter(vr_handle h, int *op, int r3[3])
+{
+    if (!h) return VR_E_INVALID;
+    h->core.getRankFilter(op, r3);
+    return VR_OK;
+}
+
+int vr_get_rank_filter_ms(vr_handle h, float *ms)
+{
+    if (!h || !ms) return VR_E_INVALID;
+    *ms = h->core.lastRankMs();
+    return VR_OK;
+}
+
 int vr_extract_isosurface(vr_handle h, int32_t iso_value, uint64_t *n_vertices, uint64_t *n_triangles)
 {
     return guarded(h, [&](vr::RendererCore &c) { c.extractIsosurface(iso_value, n_vertices, n_triangles); });

@@ -31,6 +31,7 @@ SYNTH_SPHERE_U8, SYNTH_NOISE_BALL, SYNTH_NOISE_BALL_CT = 0, 1, 2
 QUIRK_TRUNC_GRID, QUIRK_U16_OFFSET = 1, 2
 QUIRK_DEFAULT = QUIRK_U16_OFFSET
 VR_SLAB_MIP, VR_SLAB_MINIP, VR_SLAB_MEAN = 0, 1, 2     # vr_set_reslice
+VR_RANK_OFF, VR_RANK_ERODE, VR_RANK_DILATE, VR_RANK_OPEN, VR_RANK_CLOSE, VR_RANK_MEDIAN = range(6)     # vr_rank_filter_volume
 _SLAB_MODES = {"mip": VR_SLAB_MIP, "minip": VR_SLAB_MINIP, "mean": VR_SLAB_MEAN}
 
 
@@ -130,6 +131,9 @@ def load_library() -> C.CDLL:
         "vr_smooth_weights": (i32, [f32, C.POINTER(f32), i32, C.POINTER(i32)]),
         "vr_set_smoothing_workspace": (i32, [h, C.c_uint64]),
         "vr_get_smoothing_ms": (i32, [h, C.POINTER(f32)]),
+        "vr_rank_filter_volume": (i32, [h, i32, i32, i32, i32]),
+        "vr_get_rank_filter": (i32, [h, C.POINTER(i32), C.POINTER(i32)]),
+        "vr_get_rank_filter_ms": (i32, [h, C.POINTER(f32)]),
         "vr_extract_isosurface": (i32, [h, i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "vr_get_mesh_info": (i32, [h, C.POINTER(i32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "vr_read_mesh": (i32, [h, C.POINTER(f32), C.POINTER(f32), C.POINTER(C.c_uint32), C.c_uint64, C.c_uint64]),
@@ -687,6 +691,29 @@ class RendererCore:
 
     def setSmoothingWorkspace(self, nbytes):
         self._check(self._lib.vr_set_smoothing_workspace(self._h, C.c_uint64(int(nbytes))))
+
+    def rankFilterVolume(self, op, radius_voxels=1):
+        """vr_rank_filter_volume: grey-level morphology (VR_RANK_ERODE, DILATE, OPEN, CLOSE; radii 0 .. 8) or the median
+        (VR_RANK_MEDIAN; radii 0 .. 1) of the volume as loaded, over a box of radius_voxels: a number or one radius per volume
+        axis, x first.  VR_RANK_OFF or radius 0: the identity.  A Gaussian in force (smoothVolume) is applied to the result."""
+        r = np.broadcast_to(np.asarray(radius_voxels), (3,))
+        if not all(float(v) == int(v) for v in r):
+            raise ValueError("rankFilterVolume: radii are whole numbers of voxels")
+        self._check(self._lib.vr_rank_filter_volume(self._h, int(op), int(r[0]), int(r[1]), int(r[2])))
+
+    @property
+    def rankFilter(self):
+        """(op, (rx, ry, rz)) of the volume being rendered; (VR_RANK_OFF, (0, 0, 0)): no rank filter"""
+        op = C.c_int32(0)
+        r = (C.c_int32 * 3)()
+        self._check(self._lib.vr_get_rank_filter(self._h, C.byref(op), r))
+        return int(op.value), (int(r[0]), int(r[1]), int(r[2]))
+
+    def rankFilterMs(self) -> float:
+        """HIP-event time of the last rank filter's passes, ms"""
+        ms = C.c_float(0.0)
+        self._check(self._lib.vr_get_rank_filter_ms(self._h, C.byref(ms)))
+        return float(ms.value)
 
     def extractIsosurface(self, iso):
         """vr_extract_isosurface: the surface s = iso of the volume being rendered as an indexed triangle mesh, kept on the
